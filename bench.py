@@ -6,14 +6,22 @@ batch 2000, 25 negatives per positive, L2 norm, SGD (alpha 1.0, margin 5), bern 
 of 2000 positives x (1 + 25) slots, NegativeSampling + MarginLoss forward, backward, SGD update of the
 touched rows. Inputs (graph, tables) are resident in HBM before timing starts.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, instantiates the K-step graph (one untimed replay), times K steps once
+and prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (the milliseconds one
+timed step took) and the configuration. --dump-outputs DIR then writes what the timed path left after its last
+timed step (per-step losses, the trained tables) as float32 DIR/<name>.npy; graphs, tables and sampler streams are
+seeded, so the same arguments give the same inputs. Everything else is measured only with --full, after the
+headline run: further repeats of it, the deterministic mode, the per-kernel roofline, the universe fields (pu_c3
+with its drop-in leg, pu_c3_ref6000, at N > 1 pu_c3_weak and pu_c4_lp) and the CPU baselines.
 
 N > 1: bench.py runs as one rank per GPU; started without a torch.distributed environment it launches the N
 ranks itself (torch.distributed.run, 127.0.0.1) before touching the GPU and relays rank 0's line.
 
 C2 is a single model, so N > 1 runs N independent replicas (one per GPU, "replicas only", weak
 scaling, no collective in the data path); value = slots of all ranks / max-over-ranks time.
-Prints ONE JSON line on rank 0 with roofline (live HIP-event kernel timing, per-kernel counted bytes from
+With --full the line also carries roofline (live HIP-event kernel timing, per-kernel counted bytes from
 the committed PMC summary) and cpu_baseline (the oracle's C restatement on the host's cores, at most 16
 threads, timed on a bounded sample of the same workload, rank 0, N = 1); the pu_c3 field (C3 universes)
 carries its own cpu_baseline.
@@ -405,11 +413,14 @@ def chain_profile(L, us, reset, idx, time_set, mid, name, prof_on, rel_of=None, 
     return out
 
 
-def run_universes(args, ws, rank, dev, name="c3", cpu=True, per_gpu=False, check_lp=False):
+def run_universes(args, ws, rank, dev, name="c3", cpu=True, per_gpu=False, check_lp=False, dump_dir=None):
     """PuTransE / PuTransH universes placed over ranks by LPT (place_universes; no collective in training), Adagrad,
     neg 1, bern 0, filter 0, nbatches 20, 8 sampler threads. One step = every universe's full training
-    run (all its epochs) in one persistent launch. C4 adds link prediction over the test split: each
-    rank MINs its universes' scores into the key rows, one RCCL all_reduce(MIN), GPU ranking."""
+    run (all its epochs) in one persistent launch. With --full, C4 adds link prediction over the test split: each
+    rank MINs its universes' scores into the key rows, one RCCL all_reduce(MIN), GPU ranking. Without --full only
+    the timed trainings run: no chain profile, deterministic-mode timing, placement shares, link prediction or CPU
+    baseline. `dump_dir` (rank 0): the last timed training's per-epoch losses and trained tables go there."""
+    full = bool(getattr(args, "full", False))
     import synth_kg
     from openke import _native
     L = _native.lib()
@@ -505,11 +516,13 @@ def run_universes(args, ws, rank, dev, name="c3", cpu=True, per_gpu=False, check
                 _native.check(L.pt_universe_set_reset(us))
         return us, reset
 
+    last_losses = [None]
+
     def time_set(us, reset, idx, steps, warmup):
         """Seconds of `steps` trainings of the set (after `warmup` untimed ones), each from the initial state:
         the reset outside the timed region, barrier + synchronize on both sides of every timed training."""
         total_epochs = sum(int(jobs[i].epochs) for i in idx)
-        losses = torch.zeros(max(total_epochs, 1), device=dev)
+        losses = last_losses[0] = torch.zeros(max(total_epochs, 1), device=dev)
         stream = _native.stream()
         el = 0.0
         for s_ in range(warmup + steps):
@@ -556,6 +569,12 @@ def run_universes(args, ws, rank, dev, name="c3", cpu=True, per_gpu=False, check
         bytes_step = slots_step * algorithmic_bytes_per_slot(model, "adagrad", int(jobs[i_long].dim))
     uset, reset = make_set(every)
     el = time_set(uset, reset, every, args.c3_steps, args.c3_warmup)
+    if dump_dir and rank == 0:
+        # the universes' tables one after another (universe order, each row-major), ahead of any further training
+        tabs = {k: torch.cat([unis[i][k].reshape(-1) for i in every]) for k in ("ent", "rel", "nv")
+                if every and unis[every[0]][k] is not None}
+        dump_outputs(dump_dir, dict(tabs, losses=last_losses[0]))
+        del tabs
     class_launches = launch_times(uset)
     rel_of = {(int(jobs[i].batch_size), int(jobs[i].dim), int(unis[i]["ent"].shape[0])): int(unis[i]["rel"].shape[0])
               for i in every}
@@ -564,7 +583,8 @@ def run_universes(args, ws, rank, dev, name="c3", cpu=True, per_gpu=False, check
                                                  int(jobs[i].dim))) if every else None
     target = (int(jobs[i_m].batch_size), int(jobs[i_m].dim), int(unis[i_m]["ent"].shape[0]),
               int(jobs[i_m].epochs) * 20) if every else None
-    chain = chain_profile(L, uset, reset, every, time_set, mid, name, prof_on, rel_of, target) if every else None
+    chain = chain_profile(L, uset, reset, every, time_set, mid, name, prof_on, rel_of, target) \
+        if every and full else None
     tot = torch.tensor([el, float(slots_step), float(bytes_step)], dtype=torch.float64, device=dev)
     if ws > 1:
         import torch.distributed as dist
@@ -605,14 +625,14 @@ def run_universes(args, ws, rank, dev, name="c3", cpu=True, per_gpu=False, check
         print("universe-prof longest universe: %.1f Mcycles (%.1f ms at 2.4 GHz); run %.1f ms" %
               (span.max() / 1e6, span.max() / 2.4e6, el * 1e3 / args.c3_steps), file=sys.stderr)
     det_s = None
-    if args.deterministic_timing and ws == 1:
+    if full and args.deterministic_timing and ws == 1:
         # the reference-order mode (bit-identical to the oracle) on the same set, one training from the start
         _native.check(L.pt_universe_set_deterministic(uset, 1))
         det_s = time_set(uset, reset, every, 1, 0)
         _native.check(L.pt_universe_set_deterministic(uset, 0))
     _native.check(L.pt_universe_set_free(uset))
     placement = None
-    if args.place_world > 1 and ws == 1:
+    if full and args.place_world > 1 and ws == 1:
         # one GPU, the per-rank critical path of a place_world-way job: each rank's LPT share (place_universes,
         # as Parallel_Universe_Config places a wave) trained alone, from the initial state
         pw = args.place_world
@@ -665,14 +685,17 @@ def run_universes(args, ws, rank, dev, name="c3", cpu=True, per_gpu=False, check
            "universes_per_gpu": len(own), "host_universe_build_s": build_s,
            "note_runs": "every timed run trains every universe from its initial tables, Adagrad state and sampler "
                         "streams (restored before the run, outside the timed region)",
-           "roofline": dict(chain or {}, bound="chain", algorithmic_GBps_per_gpu=achieved,
+           "algorithmic_GBps_per_gpu": achieved}
+    roofline_for_set = dict(chain or {}, bound="chain", algorithmic_GBps_per_gpu=achieved,
                             note="the set ends with its longest universe, one workgroup's dependent step chain: achieved "
                                  "= that universe's measured shader cycles per step (pt_universe_set_profiling, one "
                                  "extra untimed training), floor = chain_floor's model of it (bench.py: L2 / LDS round "
                                  "trips, lane-group reductions, barriers, + VALU issue when its rocprofv3 counters are "
                                  "committed for this build), frac = floor / achieved; the floor takes L2 hits, which a "
                                  "universe alone gets (hit rate 0.997) and a full set does not (C4: 0.27, "
-                                 "profiles/r06_c4_l2.txt). algorithmic_GBps_per_gpu: SURVEY 8(d) bytes per wall second")}
+                                 "profiles/r06_c4_l2.txt). algorithmic_GBps_per_gpu: SURVEY 8(d) bytes per wall second")
+    if full:
+        out["roofline"] = roofline_for_set
     if class_launches is not None:
         out["class_launches"] = class_launches
     if det_s is not None:
@@ -682,7 +705,7 @@ def run_universes(args, ws, rank, dev, name="c3", cpu=True, per_gpu=False, check
         out["placement"] = placement
     if longest is not None:
         out["longest_universe_cycles"] = longest
-    if do_lp:
+    if do_lp and full:
         out["link_prediction"] = lp = universe_link_prediction(L, path, unis, mid, p_norm, ws, dev)
         if check_lp and ws > 1:
             # the N = 1 recomputation: every rank's trained universes gathered, rank 0 scores and ranks all of them
@@ -698,7 +721,7 @@ def run_universes(args, ws, rank, dev, name="c3", cpu=True, per_gpu=False, check
                 lp["digest_match"] = ref["rank_digest"] == lp["rank_digest"]
             del allu
     L.pt_graph_free(g)
-    if cpu and ws == 1 and rank == 0 and not args.no_cpu_baseline:
+    if full and cpu and ws == 1 and rank == 0 and not args.no_cpu_baseline:
         out["cpu_baseline"] = universe_cpu_baseline(path, name, args.cpu_seconds, getattr(args, "dim", 0),
                                                     getattr(args, "universes", 0))
     return out
@@ -907,6 +930,29 @@ def universe_link_prediction(L, path, unis, mid, p_norm, ws, dev):
             "note": "universe scoring 4D+4 B per (key, universe entity); ranking 4 B per (query, entity)"}
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: float32 payload written in all (the files stay under 64 MB)
+DUMP_WHOLE_BELOW = 65536        # arrays up to this many elements are always written whole
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: what the timed path left with its caller after its last timed step, one float32
+    DIR/<name>.npy per entry of `arrays` (name -> tensor). Within the byte budget every array is written whole;
+    past it each large array is cut to the same fraction of its elements, a sorted sample of flat indices drawn
+    with a fixed seed (numpy default_rng(0)), so two builds run with the same arguments write the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 4 * sum(int(a.numel()) for a in arrays.values())
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    rng = np.random.default_rng(0)
+    for name, a in arrays.items():
+        a = a.detach().to(torch.float32)
+        n = int(a.numel())
+        keep = n if frac >= 1.0 else min(n, max(DUMP_WHOLE_BELOW, int(n * frac)))
+        if keep < n:   # a sampled array is written flat, a whole one in its own shape
+            idx = np.sort(rng.integers(0, n, keep, dtype=np.int64))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
+
+
 def library_sha256():
     """sha256 of the library this process loaded (the product build unless tools_gpu/ablib.py swapped it)."""
     import hashlib
@@ -935,10 +981,23 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS) + sorted(PU_WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run also measure everything else this file knows: further repeats of the "
+                         "K-step run, the deterministic mode, per-kernel roofline, the universe fields (pu_c3, "
+                         "pu_c3_ref6000, drop-in, placement shares, link prediction) and the CPU baselines. Without "
+                         "it the run sets up, warms up, times --steps steps and prints the headline fields; the "
+                         "options below that select or trim those extras act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path left with its caller (the per-step losses "
+                         "and the trained tables) as float32 DIR/<name>.npy, before anything --full adds runs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--repeats", type=int, default=5, help="timed repeats of the K-step run (value = median)")
+    ap.add_argument("--repeats", type=int, default=5,
+                    help="--full: the K-step run timed this many times in all (the headline is the first; the "
+                         "median and best are reported beside it)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--data-dir", default=os.path.join(tempfile.gettempdir(), "putranse_bench"))
+    ap.add_argument("--data-dir", default=os.path.join(tempfile.gettempdir(), "putranse_bench_%d" % os.getuid()),
+                    help="where the synthetic graphs are written once (default: a per-user folder under the "
+                         "temporary directory)")
     ap.add_argument("--no-c3", action="store_true", help="skip the PuTransE universe workload (C3) field")
     ap.add_argument("--c3-steps", type=int, default=2)
     ap.add_argument("--c3-warmup", type=int, default=1)
@@ -1005,8 +1064,8 @@ def main():
     if args.workload in PU_WORKLOADS:
         dev = torch.device("cuda", torch.cuda.current_device())
         args.c3_steps, args.c3_warmup = args.steps, args.warmup
-        c3 = run_universes(args, ws, rank, dev, args.workload)
-        dropin = None if args.no_dropin else run_dropin(args, ws, rank, dev, args.workload)
+        c3 = run_universes(args, ws, rank, dev, args.workload, dump_dir=args.dump_outputs)
+        dropin = run_dropin(args, ws, rank, dev, args.workload) if args.full and not args.no_dropin else None
         if rank == 0:
             rec = {"metric": "training triples/sec (pos+neg)", "value": c3["value"], "unit": "triples/s",
                    "n_gpus": ws, "steps": args.steps, "warmup": args.warmup, "ms_per_step": c3["s_per_step"] * 1e3,
@@ -1014,7 +1073,9 @@ def main():
                    "data": "synthetic %s-shaped graph (tools/synth_kg.py, seed 0), xavier-uniform tables" %
                            PU_WORKLOADS[args.workload][0],
                    "config": {"workload": c3["workload"], "parallelism": "universes placed by LPT over %d ranks" % ws},
-                   "roofline": c3["roofline"], "universes_per_gpu": c3["universes_per_gpu"]}
+                   "universes_per_gpu": c3["universes_per_gpu"]}
+            if "roofline" in c3:
+                rec["roofline"] = c3["roofline"]
             if "link_prediction" in c3:
                 rec["link_prediction"] = c3["link_prediction"]
             if dropin is not None:
@@ -1070,10 +1131,10 @@ def main():
                                    _native.stream()))
     torch.cuda.synchronize()
 
-    # the K-step replay timed `repeats` times (each bracketed by barrier + synchronize, max over ranks); value is
-    # the median (box-to-box and run-to-run spread shows in the min / max alongside)
+    # the K-step replay, bracketed by barrier + synchronize, max over ranks: the first timed run is the headline
+    # (--steps timed steps); --full times it `repeats` times in all and reports their median and best alongside
     runs = []
-    for _ in range(max(args.repeats, 1)):
+    for rep in range(max(args.repeats, 1) if args.full else 1):
         barrier(ws)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -1088,7 +1149,44 @@ def main():
             all_reduce(tt, dist.ReduceOp.MAX)
             el = float(tt.item())
         runs.append(el)
-    el = float(np.median(runs))
+        if rep == 0:
+            loss_last = float(losses[-1].item())   # the headline run's last step
+        if rep == 0 and args.dump_outputs and rank == 0:
+            # what Trainer.run's caller holds after the headline run's last step: every timed step's loss and the
+            # model's tables, updated in place
+            dump_outputs(args.dump_outputs, dict({k: v for k, v in zip(("ent_embeddings", "rel_embeddings",
+                                                                        "norm_vector"), kge.tables())
+                                                  if v is not None}, losses=losses))
+    el = runs[0]
+    assert np.isfinite(loss_last), "non-finite loss"
+    head = {
+        "metric": "training triples/sec (pos+neg)",
+        "value": args.steps * seq * ws / el,
+        "unit": "triples/s",
+        "n_gpus": ws,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": el * 1e3 / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "data": "synthetic %s-shaped graph (tools/synth_kg.py, seed 0), xavier-uniform tables" % shape,
+        "config": {"workload": "%s %s %s-shaped dim %d p%d %s lr %g margin %g batch %d neg %d bern %d filter %d "
+                               "threads 8" % (args.workload.upper(), model, shape, dim, p, opt, lr, margin, bs, neg,
+                                              bern, filt),
+                   "global_batch": seq * ws, "slots_per_step_per_gpu": seq,
+                   "parallelism": "replicas%d" % ws if ws > 1 else "single"},
+        "loss_last_step": loss_last,
+    }
+    if not args.full:
+        # the plain run ends here: set-up, warm-up, the timed steps and the headline line
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if ws > 1:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        return
     det_ms = None
     if args.deterministic_timing:
         # the reference-order mode (Trainer(deterministic=True): bit-identical to the oracle), same K steps
@@ -1103,8 +1201,6 @@ def main():
         torch.cuda.synchronize()
         det_ms = (time.perf_counter() - t0) * 1e3 / args.steps
         _native.check(L.pt_trainer_set_deterministic(tr._native, 0))
-    loss_last = float(losses[-1].item())
-    assert np.isfinite(loss_last), "non-finite loss"
 
     # live kernel timing with HIP events on the launch stream (roofline of the fused step): the same
     # per-step kernels launched one by one with an event pair around each; per-chunk sampling/scan
@@ -1168,28 +1264,12 @@ def main():
             import torch.distributed as dist
             dist.destroy_process_group()
         return
-    value = args.steps * seq * ws / el
-    rec = {
-        "metric": "training triples/sec (pos+neg)",
-        "value": value,
-        "unit": "triples/s",
-        "n_gpus": ws,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": el * 1e3 / args.steps,
+    rec = dict(head)
+    rec.update({
         "repeats": len(runs),
         "ms_per_step_runs": [r * 1e3 / args.steps for r in runs],
+        "value_median": args.steps * seq * ws / float(np.median(runs)),
         "value_best": args.steps * seq * ws / min(runs),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "fp32",
-        "data": "synthetic %s-shaped graph (tools/synth_kg.py, seed 0), xavier-uniform tables" % shape,
-        "config": {"workload": "%s %s %s-shaped dim %d p%d %s lr %g margin %g batch %d neg %d bern %d filter %d "
-                               "threads 8" % (args.workload.upper(), model, shape, dim, p, opt, lr, margin, bs, neg,
-                                              bern, filt),
-                   "global_batch": seq * ws, "slots_per_step_per_gpu": seq,
-                   "parallelism": "replicas%d" % ws if ws > 1 else "single"},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                      "kernel": "one training step = " + " + ".join(per_kernel),
@@ -1214,8 +1294,7 @@ def main():
                              "rows written by the step kernel and read back by the apply pass (fused step + apply: by each row's last "
                              "arriving wave, in the same kernel)" %
                              (args.workload, 4e-6 * dl.get_ent_tot() * dim)},
-        "loss_last_step": loss_last,
-    }
+    })
     if det_ms is not None:
         rec["deterministic_ms_per_step"] = det_ms
         rec["deterministic_triples_per_s"] = seq * 1e3 / det_ms

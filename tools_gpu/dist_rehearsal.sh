@@ -4,6 +4,7 @@
 # ranks over RCCL, one per GPU). Checks the multi-rank path end to end (replicas, universe sharding, weak and
 # reference-scale fields) and that the line reports n_gpus 2.
 set -u
-mkdir -p gpurun_out
-PT_BENCH_BACKEND=gloo timeout -k 10 600 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline \
-  > gpurun_out/dist2.log 2>&1 || exit $?
+export RESULTS=${RESULTS:-results}   # where this script leaves its logs and summaries
+mkdir -p $RESULTS
+PT_BENCH_BACKEND=gloo timeout -k 10 600 python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline \
+  > $RESULTS/dist2.log 2>&1 || exit $?

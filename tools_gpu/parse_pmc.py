@@ -1,4 +1,4 @@
-"""Summarise rocprofv3 --pmc passes (gpurun_out/pmc/p*/run_counter_collection.csv): mean counter value
+"""Summarise rocprofv3 --pmc passes (results/pmc/p*/run_counter_collection.csv): mean counter value
 per dispatch for each kernel (first 40 chars of the name), plus the kernel-trace mean duration."""
 import csv
 import glob
@@ -7,7 +7,7 @@ import os
 import sys
 from collections import defaultdict
 
-root = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/pmc"
+root = sys.argv[1] if len(sys.argv) > 1 else "results/pmc"
 # the library the passes profiled (the product build of this tree): bench.py uses the counted bytes only when
 # this digest equals the loaded library's
 LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "openke-putranse_amd", "openke",

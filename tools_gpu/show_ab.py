@@ -6,7 +6,7 @@ import sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "ab"
 rows = {}
-for f in sorted(glob.glob("gpurun_out/%s_*_c?_?.log" % tag)):
+for f in sorted(glob.glob("results/%s_*_c?_?.log" % tag)):
     m = re.match(r".*/%s_(.+)_(c\d)_(\d)\.log" % re.escape(tag), f)
     lib, wl, rep = m.groups()
     txt = open(f).read()
