@@ -229,19 +229,16 @@ int pt_universe_set_free(pt_universe_set *s);
  * universe (in the set's launch order) shader-clock cycles spent in epoch presampling, phase A, phase B, the
  * step count, batch size, dim and entity count (last train call); out[.][7]: the universe's start on the 100 MHz
  * wall clock (low 32 bits, in the high word) and its duration in those ticks (low word); out[.][63]: where it ran -
- * its XCD (high word) and the workgroup's HW_REG_HW_ID (low word: CU, SH, SE fields); team universes: out[.][60]
- * width << 32 | one-XCD flag, [61] member 0's barrier cycles, [62] member 0's phase-B rows summed over the steps; the
+ * its XCD (high word) and the workgroup's HW_REG_HW_ID (low word: CU, SH, SE fields); out[.][60..62]
+ * (the removed team universes' width, barrier cycles and phase-B rows) stay in the layout and stay zero; the
  * other words of out[.][8..59]: phase stamps of one step of lane group 0 in the measurement build (make TUNING=1),
  * zero otherwise */
 int pt_universe_set_profiling(pt_universe_set *s, int32_t on);
-/* Team universes (csrc/universes_team.h), process-wide and read when a set is created: when a set holds fewer
- * universes than the GPU has CUs, the spare CUs train its longest universes with teams of up to `w` workgroups
- * (one step's positives and row updates split over the members; 1, 2 or 4; default 1: one workgroup each - teams
- * measured slower than one workgroup, round 6) */
+/* Compatibility shim: team universes (teams of 2 or 4 workgroups training one universe) measured slower than one
+ * workgroup at every width and were removed; every universe trains on one workgroup. The setter
+ * accepts 1 (PT_OK) and returns PT_ENOTSUP for any other width; the getter returns 1. */
 int pt_set_universe_team_width(int32_t w);
 int32_t pt_get_universe_team_width(void);
-/* universes of set s trained by teams, and the workgroups their launches take */
-int pt_universe_set_teams(const pt_universe_set *s, int64_t *team_universes, int64_t *team_workgroups);
 int pt_universe_set_profile(pt_universe_set *s, uint64_t *out);
 /* the current LCG states of job `job` (input order) of a set: `threads` values (host copy; synchronizes) */
 int pt_universe_set_states(pt_universe_set *s, int64_t job, uint64_t *out);

@@ -1,5 +1,6 @@
 // C-ABI of libputranse_hip.so (include/putranse.h): reentrant pt_* entry points and the reference's
 // Base.so symbols for the hot path, all executing batch construction / training / scoring on the GPU.
+// (The universe-set runtime, pt_universe_set_* and pt_universes_train, is universe_set.cpp.)
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -10,8 +11,6 @@
 #include <mutex>
 #include <thread>
 #include <tuple>
-#include <queue>
-#include <set>
 #include <unordered_map>
 #include <vector>
 
@@ -1148,807 +1147,6 @@ extern "C" int pt_universe_seeds(const pt_universe *u, uint64_t *seeds) {
     return PT_OK;
 }
 
-// Streams of the universe trainer's concurrent class launches: created once per device for the whole process
-// and shared by every set. Each is created with a CU mask that covers every CU: the runtime gives such a stream
-// a hardware queue of its own instead of sharing one of the process's GPU_MAX_HW_QUEUES (4) queues with the
-// caller's streams. With plain streams, a process that already held streams of its own (torch's, the C2 trainer's
-// capture stream) got two class launches on one queue, where they ran one after the other (round 4: the C3 set
-// 58.7 ms in the default bench process against 35.7 ms standalone).
-namespace {
-struct ClassStreamPool {
-    std::mutex mu;
-    std::map<std::pair<int, int>, std::vector<hipStream_t>> by_dev;   // (device, mode) -> streams
-    // destroyed when the library is unloaded (process exit): the HIP runtime, loaded before this library, is
-    // finalized after it, so the queues are released while it still runs
-    ~ClassStreamPool() {
-        for (auto &kv : by_dev) {
-            if (hipSetDevice(kv.first.first) != hipSuccess) continue;
-            for (hipStream_t q : kv.second) (void)hipStreamDestroy(q);
-        }
-    }
-};
-ClassStreamPool &class_stream_pool() {
-    static ClassStreamPool p;
-    return p;
-}
-// mode 1: full-CU-mask streams (dedicated hardware queues; the product's choice); tuning builds also take
-// PT_UNI_STREAMS = 0 (round 4: per-set plain side streams, class 0 on the caller's stream), 2 (highest-priority
-// streams: their own queue pool), 3 (plain library streams)
-int class_stream_mode() {
-    static const int m = [] {
-        const char *v = pt_tuning_env("PT_UNI_STREAMS");
-        return v ? atoi(v) : 1;
-    }();
-    return m;
-}
-hipError_t class_streams(int device, int mode, size_t n, std::vector<hipStream_t> *out) {
-    ClassStreamPool &P = class_stream_pool();
-    std::lock_guard<std::mutex> lk(P.mu);
-    auto &v = P.by_dev[{device, mode}];
-    while (v.size() < n) {
-        hipStream_t q = nullptr;
-        hipError_t e = hipSuccess;
-        if (mode == 1) {
-            int cus = 0;
-            e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-            if (e != hipSuccess) return e;
-            std::vector<uint32_t> mask((size_t)(cus + 31) / 32, 0u);
-            for (int c = 0; c < cus; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
-            e = hipExtStreamCreateWithCUMask(&q, (uint32_t)mask.size(), mask.data());
-        } else if (mode == 2) {
-            int lo = 0, hi = 0;
-            e = hipDeviceGetStreamPriorityRange(&lo, &hi);
-            if (e == hipSuccess) e = hipStreamCreateWithPriority(&q, hipStreamNonBlocking, hi);
-        } else {
-            e = hipStreamCreateWithFlags(&q, hipStreamNonBlocking);
-        }
-        if (e != hipSuccess) return e;
-        v.push_back(q);
-    }
-    out->assign(v.begin(), v.begin() + (std::ptrdiff_t)n);
-    return hipSuccess;
-}
-}  // namespace
-
-// Team universes (universes_team.h): the widest team a set may give one universe (1: none), process-wide like the
-// reference's global state; read when a set is created
-namespace {
-std::atomic<int> g_team_width{1};
-}
-extern "C" int pt_set_universe_team_width(int32_t w) {
-    PT_CHECK(w == 1 || w == 2 || w == 4, PT_EINVAL, "pt_set_universe_team_width: 1, 2 or 4");
-    g_team_width.store(w);
-    return PT_OK;
-}
-extern "C" int32_t pt_get_universe_team_width(void) { return g_team_width.load(); }
-
-
-// Train many universes with the persistent multi-universe kernel (universes.hip).
-struct pt_universe_set {
-    int32_t model = 0, p_norm = 1, norm_flag = 1, opt = PT_ADAGRAD;
-    int64_t bern = 0, filter = 0, neg = 1;
-    int device = -1;
-    void *arena = nullptr;
-    pt::UniverseDev *d_us = nullptr;      // inside the arena, by row shape, longest-first inside a shape
-    int *d_counter = nullptr;             // work-queue counters, one per shape group (inside the arena)
-    struct Group {
-        int shape;
-        int64_t off, n;
-        double work;
-        int64_t share = 1;   // workgroups (= CUs) of its launch
-        // team launch (shape class >= kUniTeamBase): [grid][2] universe (index from off) and member (-1: idle)
-        int32_t *d_map = nullptr;
-        int64_t grid = 0;
-    };
-    uint32_t *d_team_sync = nullptr;      // team universes' arrival counters (inside the arena, zeroed per call)
-    int64_t n_team_sync = 0;
-    pt::UniverseLaunch team_cfg;          // the team launches' LDS plan
-    pt::TeamDev *d_teams = nullptr;       // [host]: team universes' exchange state (inside the team arena)
-    std::vector<int> host_team_w;         // [host]: team width (1: a workgroup of its own)
-    std::vector<Group> groups;            // runs of d_us with one shape class (one kernel launch each)
-    std::vector<hipStream_t> streams;     // PT_UNI_STREAMS=0 only: per-set side streams (else the process pool's)
-    std::vector<hipEvent_t> events;
-    std::vector<hipEvent_t> t_start, t_stop;   // per group launch: timing events of the last train call
-    bool timed = false;                        // the last train call recorded them
-    pt::UniverseLaunch cfg;
-    std::vector<pt::UniverseDev> host;    // same order; loss pointers patched per train call
-    std::vector<int64_t> host_loss_off;
-    std::vector<int64_t> host_of_job;     // job index -> index in host / d_us
-    std::vector<uint64_t> seeds0;         // [host][64]: the jobs' LCG states at creation (pt_universe_set_reset)
-    void *graph_arena = nullptr;          // the universes' device graphs (one allocation, one copy)
-    uint64_t *prof = nullptr;             // PT_UNI_PROF=1: [n][64] cycle counters + shape (+ stamps) (device)
-    // reference-order (deterministic) mode (pt_universe_set_deterministic): ordered.hip's universe kernel
-    bool ordered = false;
-    void *ord_arena = nullptr;            // per universe [4][seq][dim] gradient rows
-    int64_t ord_max_seq = 0;
-    void *team_arena = nullptr;           // team universes: partials, arrival counters, launch maps
-    ~pt_universe_set() {
-        if (team_arena) (void)hipFree(team_arena);
-        for (auto e : events) (void)hipEventDestroy(e);
-        for (auto e : t_start) (void)hipEventDestroy(e);
-        for (auto e : t_stop) (void)hipEventDestroy(e);
-        for (auto q : streams) (void)hipStreamDestroy(q);
-        if (arena) (void)hipFree(arena);
-        if (prof) (void)hipFree(prof);
-        if (ord_arena) (void)hipFree(ord_arena);
-        if (graph_arena) (void)hipFree(graph_arena);
-    }
-};
-
-extern "C" int pt_universe_set_create(const pt_universe_job *jobs, int64_t n, int32_t model, int32_t p_norm,
-                                      int32_t norm_flag, int32_t opt, int64_t bern, int64_t filter,
-                                      pt_universe_set **out) {
-    PT_CHECK(out && (jobs || n == 0), PT_EINVAL, "pt_universe_set_create: null argument");
-    PT_CHECK(model == 0 || model == 1, PT_EINVAL, "model must be 0 (TransE) or 1 (TransH)");
-    PT_CHECK(p_norm == 1 || p_norm == 2, PT_EINVAL, "p_norm must be 1 or 2");
-    PT_CHECK(opt == PT_SGD || opt == PT_ADAGRAD, PT_EINVAL, "opt must be PT_SGD or PT_ADAGRAD");
-    auto set = std::make_unique<pt_universe_set>();
-    set->model = model; set->p_norm = p_norm; set->norm_flag = norm_flag; set->opt = opt;
-    set->bern = bern; set->filter = filter;
-    PT_HIP(hipGetDevice(&set->device));
-    int64_t neg = -1;
-    // layout of the per-universe workspace in one arena
-    auto al = [](int64_t b) { return (b + 255) & ~int64_t(255); };
-    struct Slot {
-        int64_t states, contrib, grad, flags;
-    };
-    std::vector<Slot> slots((size_t)n);
-    // every universe's LCG states first, 64 words each in set order (one upload, one reset copy)
-    int64_t total = al(512 * std::max<int64_t>(n, 1));
-    for (int64_t i = 0; i < n; ++i) {
-        const pt_universe_job &J = jobs[i];
-        PT_CHECK(J.graph && J.seeds && J.ent && J.rel, PT_EINVAL, "universe job: null graph / seeds / tables");
-        PT_CHECK(model == 0 || J.normv, PT_EINVAL, "TransH universe job needs normv");
-        PT_CHECK(opt == PT_SGD || (J.ent_acc && J.rel_acc && (model == 0 || J.norm_acc)), PT_EINVAL,
-                 "Adagrad universe job needs accumulators");
-        PT_CHECK(J.threads > 0 && J.threads <= 64, PT_EINVAL, "universe job: threads must be in [1, 64]");
-        PT_CHECK(J.dim > 0 && pt::universe_shape_supported(J.dim, model), PT_EINVAL, "universe job: unsupported dim");
-        PT_CHECK(J.batch_size >= 0 && J.epochs >= 0 && J.nbatches >= 0, PT_EINVAL, "universe job: negative sizes");
-        PT_CHECK(neg < 0 || J.neg == neg, PT_EINVAL, "universe jobs must share neg");
-        PT_CHECK(J.neg >= 1, PT_EINVAL, "universe job: neg must be >= 1");
-        neg = J.neg;
-        const pt::Graph &g = reinterpret_cast<const pt_graph *>(J.graph)->g;
-        PT_CHECK(g.train_total > 0 || J.batch_size == 0, PT_EINVAL, "universe job: empty graph");
-        PT_CHECK(J.batch_size * (4 + J.neg) <= 16384, PT_EINVAL, "universe job: batch too large for the LDS work list");
-        const int64_t rows = g.ent_total + g.rel_total * (model == 1 ? 2 : 1);
-        slots[i].contrib = total; total += al(4 * J.batch_size * (4 + J.neg) * J.dim);
-        slots[i].grad = total;   total += al(4 * rows * J.dim);
-        slots[i].flags = total;  total += al(4 * (g.ent_total + 2 * g.rel_total));
-    }
-    set->neg = neg < 0 ? 1 : neg;
-    const int64_t us_off = total;
-    total += al((int64_t)sizeof(pt::UniverseDev) * std::max<int64_t>(n, 1));
-    const int64_t counter_off = total;
-    total += al(sizeof(int) * 64);   // one work-queue counter per row shape
-    PT_HIP(hipMalloc(&set->arena, (size_t)total));
-    char *base = (char *)set->arena;
-    PT_HIP(hipMemset(base, 0, (size_t)us_off));
-    // LDS budget per universe workgroup: the device's per-workgroup limit, at most half a CU, minus the
-    // kernel's static LDS. (The workgroups run one per CU at 256 VGPRs, but the whole CU's LDS measured
-    // slower: C5 37.6 -> 352 ms, C4 104 -> 107 ms, C3 unchanged.)
-    int max_lds = 64 << 10;
-    (void)hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, set->device);
-    const int64_t lds_budget = std::min<int64_t>(max_lds, 80 << 10) - 1024 - 2048;   // (2 KB: the static PreTables)
-    // one persistent launch per row shape, its universes longest dependent step chain first (the work
-    // queue then approximates longest-processing-time scheduling over the launch's workgroups)
-    // A universe's time (the CU-share model and the queue order): steps x cycles per step, a fixed part plus a
-    // per-positive part that grows with the padded row (lanes x floats per lane) - fitted to every universe's
-    // measured cycles per step (r04, PT_UNI_PROF dumps of C3 and C4: 6,587 + bs x (63.3 + 0.681 x row slots);
-    // residual spread 18 % / 14 %, against 21 % / 20 % for the earlier fixed + rounds-of-positives model)
-    auto work = [&](int64_t i) {
-        const int rs = pt::universe_shape_row_slots(pt::universe_shape_id(jobs[i].dim, model));
-        return (double)jobs[i].epochs * (double)jobs[i].nbatches *
-               (6587.0 + (double)std::max<int64_t>(jobs[i].batch_size, 1) * (63.3 + 0.681 * rs));
-    };
-    std::vector<int64_t> order((size_t)n);
-    for (int64_t i = 0; i < n; ++i) order[i] = i;
-    // Kernel (class) per universe: its row shape's class kernel, or - for up to three "hot" shapes of class 1
-    // (TransE), those holding the set's longest universes - a kernel compiled for that shape alone. A class
-    // kernel is register-allocated for all its shapes at once: the longest C3 universe's shape alone runs its
-    // chain in 78 instead of 94 Mcycles. At most four launches in all (the hardware queues a process gets).
-    std::vector<int> cls_v((size_t)n);
-    std::vector<int> team_w;
-    {
-        std::vector<int> shape_v((size_t)n);
-        std::map<int, double> hot_cost;   // class-1 shape -> its longest universe (steps x (4 + rounds))
-        for (int64_t i = 0; i < n; ++i) {
-            shape_v[i] = pt::universe_shape_id(jobs[i].dim, model);
-            cls_v[i] = pt::universe_shape_class(shape_v[i]);
-            if (model != PT_TRANSE || cls_v[i] != 1) continue;
-            const int64_t gpb = pt::universe_shape_groups(shape_v[i], model);
-            const double c = (double)jobs[i].epochs * (double)jobs[i].nbatches *
-                             (4.0 + (double)((std::max<int64_t>(jobs[i].batch_size, 1) + gpb - 1) / gpb));
-            hot_cost[shape_v[i]] = std::max(hot_cost[shape_v[i]], c);
-        }
-        std::vector<std::pair<double, int>> cand;
-        for (auto &kv : hot_cost) cand.push_back({kv.second, kv.first});
-        std::sort(cand.begin(), cand.end(), std::greater<std::pair<double, int>>());
-        std::set<int> hot;
-        for (auto &c : cand) {
-            if (hot.size() >= 3) break;
-            std::set<int> h2 = hot;
-            h2.insert(c.second);
-            std::set<int> launches;
-            for (int64_t i = 0; i < n; ++i)
-                launches.insert(h2.count(shape_v[i]) ? pt::kUniHotBase + shape_v[i] : cls_v[i]);
-            if (launches.size() > 4) break;
-            hot = h2;
-        }
-        if (const char *v = pt_tuning_env("PT_UNI_HOT"))   // tuning: 0 = class kernels only
-            if (atoi(v) == 0) hot.clear();
-        for (int64_t i = 0; i < n; ++i)
-            if (hot.count(shape_v[i])) cls_v[i] = pt::kUniHotBase + shape_v[i];
-        // Teams (universes_team.h): with fewer universes than CUs the set's makespan is its longest chain and CUs
-        // idle. The spare CUs go, two at a time, to the universe whose modelled time is longest: its team doubles
-        // (1 -> 2 -> 4 workgroups, modelled speed-ups kTeamSpeed), as long as a team universe's LDS plan fits and
-        // at most two row shapes take teams (one launch per shape).
-        int cus_t = 0;
-        PT_HIP(hipDeviceGetAttribute(&cus_t, hipDeviceAttributeMultiprocessorCount, set->device));
-        const int wmax = g_team_width.load();
-        team_w.assign((size_t)n, 1);
-        if (model == PT_TRANSE && wmax > 1 && n < cus_t) {
-            static const double kTeamSpeed[5] = {0.0, 1.0, 1.6, 0.0, 2.4};
-            std::vector<bool> ok((size_t)n, false);
-            int64_t cap = 1;   // the set's work-list capacity (its largest batch)
-            for (int64_t i = 0; i < n; ++i) cap = std::max<int64_t>(cap, jobs[i].batch_size * (4 + jobs[i].neg));
-            for (int64_t i = 0; i < n; ++i)
-                ok[i] = pt::universe_team_shape(shape_v[i], model) && jobs[i].batch_size > 0 &&
-                        jobs[i].epochs * jobs[i].nbatches > 0;
-            // the team launch's LDS with one presampled batch, over its universes' largest sizes (the launch gets as
-            // many batches as then fit)
-            int64_t m_rel = 0, m_ent = 0, m_slots = 0, m_seq = 0, m_rstep = 0, m_dim = 0;
-            auto fits_with = [&](int64_t i) {
-                const pt::Graph &g = reinterpret_cast<const pt_graph *>(jobs[i].graph)->g;
-                const int64_t b = jobs[i].batch_size;
-                return pt::universe_team_lds_bytes(cap, std::max(m_rel, g.rel_total), std::max(m_ent, g.ent_total),
-                                                   std::max(m_slots, b * (2 + jobs[i].neg)),
-                                                   1, std::max(m_seq, b * (1 + jobs[i].neg)),
-                                                   std::max(m_rstep, std::min(b, g.rel_total)),
-                                                   std::max(m_dim, jobs[i].dim)) <= lds_budget;
-            };
-            int64_t spare = (int64_t)cus_t - n;
-            auto t_of = [&](int64_t i) { return work(i) / kTeamSpeed[team_w[(size_t)i]]; };
-            while (spare > 0) {
-                int64_t best = -1;
-                for (int64_t i = 0; i < n; ++i)
-                    if (best < 0 || t_of(i) > t_of(best)) best = i;
-                if (best < 0 || !ok[best] || team_w[best] >= wmax) break;   // the longest cannot get faster
-                const int64_t cost = team_w[best];
-                if (cost > spare) break;
-                std::set<int> shapes;
-                for (int64_t i = 0; i < n; ++i)
-                    if (team_w[i] > 1 || i == best) shapes.insert(shape_v[i]);
-                if (shapes.size() > 2 || (team_w[best] == 1 && !fits_with(best))) break;
-                if (team_w[best] == 1) {
-                    const pt::Graph &g = reinterpret_cast<const pt_graph *>(jobs[best].graph)->g;
-                    m_rel = std::max(m_rel, g.rel_total);
-                    m_ent = std::max(m_ent, g.ent_total);
-                    m_slots = std::max(m_slots, jobs[best].batch_size * (2 + jobs[best].neg));
-                    m_seq = std::max(m_seq, jobs[best].batch_size * (1 + jobs[best].neg));
-                    m_rstep = std::max(m_rstep, std::min(jobs[best].batch_size, g.rel_total));
-                    m_dim = std::max(m_dim, jobs[best].dim);
-                }
-                team_w[best] *= 2;
-                spare -= cost;
-            }
-            if (const char *v = pt_tuning_env("PT_UNI_TEAMS"))   // tuning: 0 = no teams
-                if (atoi(v) == 0) team_w.assign((size_t)n, 1);
-            for (int64_t i = 0; i < n; ++i)
-                if (team_w[i] > 1) cls_v[i] = pt::kUniTeamBase + shape_v[i];
-        }
-    }
-    auto cls_of = [&](int64_t i) { return cls_v[(size_t)i]; };
-    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-        const int sa = cls_of(a), sb = cls_of(b);
-        if (sa != sb) return sa < sb;
-        return work(a) > work(b);
-    });
-    for (int64_t k = 0; k < n; ++k) {
-        const int sh = cls_of(order[k]);
-        if (set->groups.empty() || set->groups.back().shape != sh) set->groups.push_back({sh, k, 0, 0.0});
-        set->groups.back().n += 1;
-        set->groups.back().work += work(order[k]);
-    }
-    PT_CHECK(set->groups.size() <= 64, PT_EINVAL, "too many universe shape classes");
-    // a team launch takes one CU per member of its universes
-    auto is_team = [&](size_t k) { return set->groups[k].shape >= pt::kUniTeamBase; };
-    for (size_t k = 0; k < set->groups.size(); ++k) {
-        if (!is_team(k)) continue;
-        int64_t w = 0;
-        for (int64_t q = set->groups[k].off; q < set->groups[k].off + set->groups[k].n; ++q) w += team_w[order[q]];
-        set->groups[k].share = w;
-    }
-    // CU shares: a universe's time by the step-cost model (`work`); give every group one CU,
-    // then each further CU to the group whose LPT makespan over its current share is longest (the launches run
-    // concurrently, so the slowest group ends the set)
-    {
-        int cus = 0;
-        PT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, set->device));
-        // (the step-cost model of `work`: with it the shares no longer leave C3's float4 hot launch ending 2 ms after
-        // the longest universe, which the rounds-of-positives model did)
-        std::vector<std::vector<double>> tg(set->groups.size());
-        for (size_t k = 0; k < set->groups.size(); ++k) {
-            const auto &gr = set->groups[k];
-            for (int64_t q = gr.off; q < gr.off + gr.n; ++q) tg[k].push_back(work(order[q]));
-            std::sort(tg[k].begin(), tg[k].end(), std::greater<double>());
-        }
-        auto makespan = [&](size_t k, int64_t s) {
-            std::priority_queue<double, std::vector<double>, std::greater<double>> m;
-            for (int64_t i = 0; i < s; ++i) m.push(0.0);
-            double end = 0;
-            for (double t : tg[k]) {
-                const double f = m.top() + t;
-                m.pop();
-                m.push(f);
-                end = std::max(end, f);
-            }
-            return end;
-        };
-        std::vector<double> ms(set->groups.size());
-        int64_t left = (int64_t)cus;
-        for (size_t k = 0; k < set->groups.size(); ++k) {
-            ms[k] = makespan(k, 1);
-            left -= set->groups[k].share;
-        }
-        for (; left > 0; --left) {
-            size_t best = set->groups.size();
-            for (size_t k = 0; k < set->groups.size(); ++k)
-                if (!is_team(k) && set->groups[k].share < set->groups[k].n &&
-                    (best == set->groups.size() || ms[k] > ms[best]))
-                    best = k;
-            if (best == set->groups.size()) break;
-            set->groups[best].share += 1;
-            ms[best] = makespan(best, set->groups[best].share);
-        }
-    }
-    set->d_us = (pt::UniverseDev *)(base + us_off);
-    set->d_counter = (int *)(base + counter_off);
-    set->host.reserve((size_t)n);
-    int64_t loss_off = 0;
-    std::vector<int64_t> loss_of((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-        loss_of[i] = loss_off;
-        loss_off += jobs[i].epochs;
-    }
-    // the universes' device graphs: host images built on worker threads (each distinct graph once), placed in
-    // one allocation with one copy
-    std::vector<const pt::Graph *> uniq;
-    std::vector<int64_t> gidx((size_t)n);
-    {
-        std::unordered_map<const pt::Graph *, int64_t> seen;
-        for (int64_t i = 0; i < n; ++i) {
-            const pt::Graph *gp = &reinterpret_cast<const pt_graph *>(jobs[i].graph)->g;
-            auto it = seen.find(gp);
-            if (it == seen.end()) {
-                it = seen.emplace(gp, (int64_t)uniq.size()).first;
-                uniq.push_back(gp);
-            }
-            gidx[i] = it->second;
-        }
-    }
-    std::vector<std::vector<char>> images(uniq.size());
-    {
-        std::atomic<int64_t> next{0};
-        auto work = [&]() {
-            for (int64_t k; (k = next.fetch_add(1)) < (int64_t)uniq.size();)
-                images[k] = const_cast<pt::Graph *>(uniq[k])->device_image();
-        };
-        const int64_t nw = std::min<int64_t>(std::max(1u, std::thread::hardware_concurrency()), 16);
-        std::vector<std::thread> pool;
-        for (int64_t w = 1; w < std::min<int64_t>(nw, (int64_t)uniq.size()); ++w) pool.emplace_back(work);
-        work();
-        for (auto &th : pool) th.join();
-    }
-    std::vector<int64_t> goff(uniq.size() + 1, 0);
-    for (size_t k = 0; k < uniq.size(); ++k) goff[k + 1] = goff[k] + al((int64_t)images[k].size());
-    {
-        std::vector<char> staging((size_t)std::max<int64_t>(goff.back(), 1));
-        for (size_t k = 0; k < uniq.size(); ++k) memcpy(staging.data() + goff[k], images[k].data(), images[k].size());
-        PT_HIP(hipMalloc(&set->graph_arena, staging.size()));
-        PT_HIP(hipMemcpy(set->graph_arena, staging.data(), staging.size(), hipMemcpyHostToDevice));
-    }
-    int64_t max_bs = 0, max_relg = 0, max_ent = 0, max_rel = 0, max_seq = 0, max_nb = 0;
-    set->seeds0.assign((size_t)(64 * std::max<int64_t>(n, 1)), 0);
-    for (int64_t i : order) {
-        const pt_universe_job &J = jobs[i];
-        const pt::Graph &g = *uniq[(size_t)gidx[i]];
-        const int64_t k = (int64_t)set->host.size();   // position in the set
-        pt::UniverseDev U{};
-        U.g = g.bind_image((char *)set->graph_arena + goff[(size_t)gidx[i]]);
-        U.states = (uint64_t *)(base + 512 * k);
-        std::copy(J.seeds, J.seeds + J.threads, set->seeds0.begin() + 64 * k);
-        U.ent = J.ent; U.rel = J.rel; U.normv = J.normv;
-        U.ent_acc = J.ent_acc; U.rel_acc = J.rel_acc; U.norm_acc = J.norm_acc;
-        float *gr = (float *)(base + slots[i].grad);
-        U.gent = gr;
-        U.grel = gr + g.ent_total * J.dim;
-        U.gnorm = model == 1 ? U.grel + g.rel_total * J.dim : nullptr;
-        int32_t *fl = (int32_t *)(base + slots[i].flags);
-        U.fent = fl;
-        U.frel = fl + g.ent_total;
-        U.fnorm = U.frel + g.rel_total;
-        U.contrib = (float *)(base + slots[i].contrib);
-        U.losses = nullptr;
-        U.prof = nullptr;   // pt_universe_set_profiling
-        U.threads = J.threads; U.bs = J.batch_size; U.nbatches = J.nbatches; U.epochs = J.epochs; U.dim = J.dim;
-        U.lr = J.lr; U.margin = J.margin;
-        U.shape = pt::universe_shape_id(J.dim, model);
-        if (set->host_of_job.empty()) set->host_of_job.assign((size_t)n, -1);
-        set->host_of_job[(size_t)i] = (int64_t)set->host.size();
-        set->host.push_back(U);
-        set->host_team_w.push_back(team_w.empty() ? 1 : team_w[(size_t)i]);
-        set->host_loss_off.push_back(loss_of[i]);
-        max_bs = std::max(max_bs, J.batch_size);
-        max_relg = std::max(max_relg, g.rel_total * J.dim);
-        max_ent = std::max(max_ent, g.ent_total);
-        max_rel = std::max(max_rel, g.rel_total);
-        max_seq = std::max(max_seq, J.batch_size * (1 + J.neg));
-        max_nb = std::max(max_nb, J.nbatches);
-    }
-    if (n > 0) PT_HIP(hipMemcpy(base, set->seeds0.data(), 8 * set->seeds0.size(), hipMemcpyHostToDevice));
-    // LDS plan (within the device's per-workgroup limit and half a CU): the work list is required;
-    // then, each if it still fits, the relation gradient rows (the contended rows of the scatter), the
-    // entity contribution lists (replace the entity float atomics), the touched flags, and as many
-    // presampled batches as fit
-    auto &C = set->cfg;
-    C.list_cap = std::max<int64_t>(max_bs * (4 + set->neg), 1);
-    auto a4 = [](int64_t v) { return 4 * ((v + 3) & ~int64_t(3)); };
-    const int64_t list_b = a4(C.list_cap);
-    const int64_t relg_b = 4 * max_relg * (model == 1 ? 2 : 1);
-    int64_t used = list_b;
-    auto env_on = [](const char *name) {
-        const char *v = pt_tuning_env(name);
-        return !v || atoi(v) != 0;
-    };
-    PT_CHECK(used <= lds_budget, PT_EINVAL, "universe batch too large for the LDS work list");
-    const int64_t per_batch = 12 * max_seq;
-    // entity rows as contribution lists (heads for entities and relations, next per slot)
-    const int64_t heads_b = a4(max_ent + 2 * max_rel) + a4(max_bs * (4 + set->neg));
-    C.contrib = used + heads_b <= lds_budget && env_on("PT_UNI_CONTRIB");
-    used += C.contrib ? heads_b : 0;
-    // relation rows: LDS gradient rows (hot rows, few) if they fit, else contribution lists
-    C.lds_relgrad = used + relg_b <= lds_budget && env_on("PT_UNI_RELGRAD");
-    C.rel_list = C.contrib && !C.lds_relgrad;
-    used += C.lds_relgrad ? relg_b : 0;
-    // touched flags of the rows that are not lists
-    const int64_t nfl = (C.contrib ? 0 : max_ent) + (C.rel_list ? 0 : 2 * max_rel);
-    const int64_t flags_b = a4(nfl);
-    C.lds_flags = nfl > 0 && used + flags_b <= lds_budget && env_on("PT_UNI_LDSFLAGS");
-    used += C.lds_flags ? flags_b : 0;
-    C.pchunk = env_on("PT_UNI_PRESAMPLE") && per_batch > 0 ? std::min<int64_t>(max_nb, (lds_budget - used) / per_batch)
-                                                            : 0;
-    if (C.pchunk < 0) C.pchunk = 0;
-    used += C.pchunk * per_batch;
-    C.lds_bytes = used;
-    // agent-scope fences only while some gradient row is a global float atomic (or a flag global)
-    C.agent_fence = !(C.contrib && (C.rel_list || (C.lds_relgrad && C.lds_flags)));
-    if (const char *v = pt_tuning_env("PT_UNI_FENCE")) C.agent_fence = C.agent_fence || atoi(v) != 0;
-    C.threads = 512;
-    // tuning overrides (benchmarks): PT_UNI_RELGRAD / CONTRIB / LDSFLAGS / PRESAMPLE = 0 disable the
-    // LDS placements above, PT_UNI_FENCE=1 forces agent-scope fences
-    // Team launches (universes_team.h): their LDS plan (every universe's presampled batches, as many as fit), one
-    // arena for the relation / loss partials and arrival counters of their universes and the launch maps, each team's
-    // members on blocks of one residue mod 8 (the dispatcher's round-robin over the XCDs: one L2 for the team -
-    // performance only, the protocol does not depend on it)
-    {
-        int64_t t_rel = 0, t_ent = 0, t_slots = 0, t_seq = 0, t_nb = 0, t_rstep = 0, t_dim = 0, part_b = 0, n_team = 0,
-                map_b = 0;
-        // a team universe's partials: [W][R][D] relation rows, [W][epochs] losses, [W] XCD ids
-        auto part_bytes = [&](const pt::UniverseDev &U, int w) {
-            return al(4 * (w * U.g.rel_total * U.dim + w * U.epochs + w));
-        };
-        std::vector<int64_t> grid_of(set->groups.size(), 0);
-        std::vector<std::vector<int32_t>> maps(set->groups.size());
-        for (size_t k = 0; k < set->groups.size(); ++k) {
-            const auto &gr = set->groups[k];
-            if (gr.shape < pt::kUniTeamBase) continue;
-            std::vector<std::pair<int, int64_t>> teams;   // (members, index from off)
-            for (int64_t q = gr.off; q < gr.off + gr.n; ++q) {
-                const pt::UniverseDev &U = set->host[(size_t)q];
-                const int w = set->host_team_w[(size_t)q];
-                teams.push_back({w, q - gr.off});
-                t_rel = std::max(t_rel, U.g.rel_total);
-                t_ent = std::max(t_ent, U.g.ent_total);
-                t_slots = std::max(t_slots, U.bs * (2 + set->neg));
-                t_seq = std::max(t_seq, U.bs * (1 + set->neg));
-                t_nb = std::max(t_nb, U.nbatches);
-                t_rstep = std::max(t_rstep, std::min(U.bs, U.g.rel_total));
-                t_dim = std::max(t_dim, U.dim);
-                part_b += part_bytes(U, w);
-                ++n_team;
-            }
-            std::stable_sort(teams.begin(), teams.end(), [](const std::pair<int, int64_t> &a,
-                                                            const std::pair<int, int64_t> &b) { return a.first > b.first; });
-            int64_t used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            std::vector<std::pair<int64_t, std::pair<int32_t, int32_t>>> blocks;
-            for (const auto &t : teams) {
-                int x = 0;
-                for (int c = 1; c < 8; ++c)
-                    if (used[c] < used[x]) x = c;
-                for (int m = 0; m < t.first; ++m) blocks.push_back({x + 8 * (used[x] + m), {(int32_t)t.second, m}});
-                used[x] += t.first;
-            }
-            int64_t rows = 0;
-            for (int c = 0; c < 8; ++c) rows = std::max(rows, used[c]);
-            grid_of[k] = 8 * rows;
-            maps[k].assign((size_t)(2 * grid_of[k]), -1);
-            for (const auto &b : blocks) {
-                maps[k][(size_t)(2 * b.first)] = b.second.first;
-                maps[k][(size_t)(2 * b.first + 1)] = b.second.second;
-            }
-            map_b += al(4 * (int64_t)maps[k].size());
-        }
-        if (n_team > 0) {
-            auto &T = set->team_cfg;
-            T = C;
-            const int64_t fixed = pt::universe_team_lds_bytes(C.list_cap, t_rel, t_ent, t_slots, 0, t_seq, t_rstep, t_dim);
-            T.pchunk = std::min<int64_t>(t_nb, (lds_budget - fixed) / std::max<int64_t>(12 * t_seq, 1));
-            PT_CHECK(T.pchunk >= 1, PT_EINVAL, "team universes: LDS plan does not fit");
-            T.lds_bytes = pt::universe_team_lds_bytes(C.list_cap, t_rel, t_ent, t_slots, T.pchunk, t_seq, t_rstep, t_dim);
-            const int64_t sync_b = al(4 * (n_team + 1));   // + the error word
-            const int64_t teams_b = al((int64_t)sizeof(pt::TeamDev) * (int64_t)set->host.size());
-            PT_HIP(hipMalloc(&set->team_arena, (size_t)(part_b + sync_b + map_b + teams_b)));
-            char *tb = (char *)set->team_arena;
-            set->d_team_sync = (uint32_t *)(tb + part_b);
-            set->n_team_sync = n_team;
-            int64_t po = 0, si = 0, mo = part_b + sync_b;
-            std::vector<pt::TeamDev> th(set->host.size(), pt::TeamDev{nullptr, nullptr, nullptr, 1});
-            for (size_t k = 0; k < set->groups.size(); ++k) {
-                auto &gr = set->groups[k];
-                if (gr.shape < pt::kUniTeamBase) continue;
-                for (int64_t q = gr.off; q < gr.off + gr.n; ++q) {
-                    pt::TeamDev &T = th[(size_t)q];
-                    T.w = set->host_team_w[(size_t)q];
-                    T.part = (float *)(tb + po);
-                    po += part_bytes(set->host[(size_t)q], T.w);
-                    T.sync = set->d_team_sync + si++;
-                    T.err = set->d_team_sync + n_team;
-                }
-                gr.d_map = (int32_t *)(tb + mo);
-                gr.grid = grid_of[k];
-                PT_HIP(hipMemcpy(gr.d_map, maps[k].data(), 4 * maps[k].size(), hipMemcpyHostToDevice));
-                mo += al(4 * (int64_t)maps[k].size());
-            }
-            set->d_teams = (pt::TeamDev *)(tb + mo);
-            PT_HIP(hipMemcpy(set->d_teams, th.data(), sizeof(pt::TeamDev) * th.size(), hipMemcpyHostToDevice));
-        }
-    }
-    *out = set.release();
-    return PT_OK;
-}
-
-extern "C" int pt_universe_set_deterministic(pt_universe_set *set, int32_t on) {
-    PT_CHECK(set, PT_EINVAL, "null universe set");
-    // the set enters reference-order mode only once its workspace exists: a failed call leaves the mode as it
-    // was (a later train call then runs the fast kernel, never the ordered one without its arena)
-    if (!on || set->host.empty() || set->ord_arena) {
-        set->ordered = on != 0;
-        return PT_OK;
-    }
-    auto al = [](int64_t b) { return (b + 255) & ~int64_t(255); };
-    int64_t total = 0, max_seq = 0;
-    std::vector<int64_t> off(set->host.size());
-    for (size_t i = 0; i < set->host.size(); ++i) {
-        const pt::UniverseDev &U = set->host[i];
-        const int64_t seq = U.bs * (1 + set->neg);
-        off[i] = total;
-        total += al(16 * seq * U.dim);
-        max_seq = std::max(max_seq, seq);
-    }
-    // the launch's LDS (dynamic plan + the kernel's static variables) against the per-workgroup limit
-    int blk_lds = 64 << 10;
-    (void)hipDeviceGetAttribute(&blk_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, set->device);
-    size_t static_lds = 0;
-    PT_HIP(pt::ordered_universe_static_lds(&static_lds));
-    PT_CHECK(pt::ordered_universe_lds_bytes(max_seq) + (int64_t)static_lds <= (int64_t)blk_lds, PT_ENOTSUP,
-             "reference-order mode: universe batch too large for the LDS plan");
-    void *arena = nullptr;
-    PT_HIP(hipMalloc(&arena, (size_t)std::max<int64_t>(total, 256)));
-    set->ord_arena = arena;
-    for (size_t i = 0; i < set->host.size(); ++i) set->host[i].ord = (float *)((char *)set->ord_arena + off[i]);
-    set->ord_max_seq = max_seq;
-    set->ordered = true;
-    return PT_OK;
-}
-
-extern "C" int pt_universe_set_train(pt_universe_set *set, float *d_losses, void *stream) {
-    PT_CHECK(set, PT_EINVAL, "null universe set");
-    if (set->host.empty()) return PT_OK;
-    hipStream_t st = (hipStream_t)stream;
-    for (size_t i = 0; i < set->host.size(); ++i)
-        set->host[i].losses = d_losses ? d_losses + set->host_loss_off[i] : nullptr;
-    PT_HIP(hipMemcpyAsync(set->d_us, set->host.data(), sizeof(pt::UniverseDev) * set->host.size(),
-                          hipMemcpyHostToDevice, st));
-    if (set->ordered) {
-        int cus = 0;
-        PT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, set->device));
-        const hipError_t e = pt::launch_universes_ordered(set->d_us, (int64_t)set->host.size(), set->d_counter, cus,
-                                                          set->model, set->p_norm, set->norm_flag, set->opt, set->neg,
-                                                          (int)set->bern, (int)set->filter, set->ord_max_seq, st);
-        if (e != hipSuccess) return pt::fail(PT_EHIP, std::string("launch_universes_ordered: ") + hipGetErrorString(e));
-        PT_HIP(hipStreamSynchronize(st));
-        return PT_OK;
-    }
-    // one launch per shape class, concurrently, each over its share of the CUs (set at creation): forked from `st`
-    // onto the process's class streams (each on a hardware queue of its own, class_streams) and joined back, so
-    // the launches overlap whatever streams the caller's process already holds
-    const size_t ng = set->groups.size();
-    const int smode = class_stream_mode();
-    std::vector<hipStream_t> qs(ng);
-    if (smode == 0) {   // round 4's scheme (tuning A/B): class 0 on `st`, the others on per-set side streams
-        while (set->streams.size() + 1 < ng) {
-            hipStream_t q;
-            PT_HIP(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
-            set->streams.push_back(q);
-        }
-        for (size_t k = 0; k < ng; ++k) qs[k] = k == 0 ? st : set->streams[k - 1];
-    } else {
-        PT_HIP(class_streams(set->device, smode, ng, &qs));
-    }
-    while (set->events.size() < ng + 1) {
-        hipEvent_t ev;
-        PT_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        set->events.push_back(ev);
-    }
-    while (set->t_start.size() < ng) {
-        hipEvent_t a, b;
-        PT_HIP(hipEventCreate(&a));
-        PT_HIP(hipEventCreate(&b));
-        set->t_start.push_back(a);
-        set->t_stop.push_back(b);
-    }
-    if (set->n_team_sync > 0) PT_HIP(hipMemsetAsync(set->d_team_sync, 0, 4 * (set->n_team_sync + 1), st));
-    PT_HIP(hipEventRecord(set->events[0], st));
-    for (size_t k = 0; k < ng; ++k)
-        if (qs[k] != st) PT_HIP(hipStreamWaitEvent(qs[k], set->events[0], 0));
-    for (size_t k = 0; k < ng; ++k) {
-        const auto &gr = set->groups[k];
-        const int64_t share = gr.share;
-        hipStream_t q = qs[k];
-        PT_HIP(hipEventRecord(set->t_start[k], q));
-        // PT_UNI_GRID=1 (tuning): one workgroup per universe in every launch, the hardware dispatcher
-        // interleaving the class launches as CUs free up, instead of a CU share per launch
-        static const bool per_universe = [] {
-            const char *v = pt_tuning_env("PT_UNI_GRID");
-            return v && atoi(v) != 0;
-        }();
-        if (gr.shape >= pt::kUniTeamBase) {
-            const hipError_t e = pt::launch_universes_team(set->d_us + gr.off, set->d_teams + gr.off, gr.d_map, gr.grid,
-                                                           gr.shape - pt::kUniTeamBase, set->p_norm, set->norm_flag,
-                                                           set->opt, set->neg, (int)set->bern, (int)set->filter,
-                                                           set->team_cfg, q);
-            if (e != hipSuccess) return pt::fail(PT_EHIP, std::string("launch_universes_team: ") + hipGetErrorString(e));
-            PT_HIP(hipEventRecord(set->t_stop[k], q));
-            continue;
-        }
-        const hipError_t e = pt::launch_universes(set->d_us + gr.off, gr.n, set->d_counter + k, gr.shape,
-                                                  per_universe ? gr.n : share,
-                                                  set->model, set->p_norm, set->norm_flag, set->opt, set->neg,
-                                                  (int)set->bern, (int)set->filter, set->cfg, q);
-        if (e != hipSuccess) return pt::fail(PT_EHIP, std::string("launch_universes: ") + hipGetErrorString(e));
-        PT_HIP(hipEventRecord(set->t_stop[k], q));
-    }
-    for (size_t k = 0; k < ng; ++k) {
-        if (qs[k] == st) continue;
-        PT_HIP(hipEventRecord(set->events[k + 1], qs[k]));
-        PT_HIP(hipStreamWaitEvent(st, set->events[k + 1], 0));
-    }
-    // the host array must outlive the async copy: this call returns only after it has been consumed
-    PT_HIP(hipStreamSynchronize(st));
-    set->timed = true;
-    if (set->n_team_sync > 0) {
-        uint32_t err = 0;
-        PT_HIP(hipMemcpy(&err, set->d_team_sync + set->n_team_sync, 4, hipMemcpyDeviceToHost));
-        PT_CHECK(err == 0, PT_EHIP, "team universes: a team member never arrived (workgroups not co-resident)");
-    }
-    return PT_OK;
-}
-
-// the class launches of the last fast-path train call: per launch its start and end (ms after the earliest start,
-// HIP events on the launch's stream) and its universe count; the launches overlap when they run concurrently
-extern "C" int pt_universe_set_launch_times(pt_universe_set *set, int64_t cap, float *out, int64_t *n_out) {
-    PT_CHECK(set && n_out, PT_EINVAL, "pt_universe_set_launch_times: null argument");
-    const int64_t ng = set->timed ? (int64_t)set->groups.size() : 0;
-    *n_out = ng;
-    if (!out || ng == 0) return PT_OK;
-    PT_CHECK(cap >= ng, PT_EINVAL, "pt_universe_set_launch_times: cap below the launch count");
-    for (int64_t k = 0; k < ng; ++k) {
-        float a = 0.f, b = 0.f;
-        PT_HIP(hipEventElapsedTime(&a, set->t_start[0], set->t_start[(size_t)k]));
-        PT_HIP(hipEventElapsedTime(&b, set->t_start[0], set->t_stop[(size_t)k]));
-        out[3 * k] = a;
-        out[3 * k + 1] = b;
-        out[3 * k + 2] = (float)set->groups[(size_t)k].n;
-    }
-    float lo = out[0];
-    for (int64_t k = 1; k < ng; ++k) lo = std::min(lo, out[3 * k]);
-    for (int64_t k = 0; k < ng; ++k) {
-        out[3 * k] -= lo;
-        out[3 * k + 1] -= lo;
-    }
-    return PT_OK;
-}
-
-// how the set trains: universes in team launches and the workgroups (CUs) those take
-extern "C" int pt_universe_set_teams(const pt_universe_set *set, int64_t *team_universes, int64_t *team_workgroups) {
-    PT_CHECK(set && team_universes && team_workgroups, PT_EINVAL, "pt_universe_set_teams: null argument");
-    *team_universes = 0;
-    *team_workgroups = 0;
-    for (const auto &gr : set->groups)
-        if (gr.shape >= pt::kUniTeamBase) {
-            *team_universes += gr.n;
-            *team_workgroups += gr.share;
-        }
-    return PT_OK;
-}
-
-// the sampler streams back to the jobs' creation states (a benchmark re-runs the same training from the same
-// start: the caller restores the tables and optimizer state)
-// whether universes of this dim train on the fast path (its row shape is compiled into its class kernel)
-extern "C" int pt_universe_dim_supported(int64_t dim, int32_t model) {
-    return (model == PT_TRANSE || model == PT_TRANSH) && pt::universe_shape_supported(dim, model) ? 1 : 0;
-}
-
-extern "C" int pt_universe_set_reset(pt_universe_set *set) {
-    PT_CHECK(set, PT_EINVAL, "null universe set");
-    if (!set->host.empty())   // the states block at the arena's start, in set order
-        PT_HIP(hipMemcpy(set->arena, set->seeds0.data(), 8 * set->seeds0.size(), hipMemcpyHostToDevice));
-    return PT_OK;
-}
-
-extern "C" int pt_universe_set_states(pt_universe_set *set, int64_t job, uint64_t *out) {
-    PT_CHECK(set && out, PT_EINVAL, "pt_universe_set_states: null argument");
-    PT_CHECK(job >= 0 && job < (int64_t)set->host_of_job.size(), PT_EINVAL, "pt_universe_set_states: bad job index");
-    const pt::UniverseDev &U = set->host[(size_t)set->host_of_job[(size_t)job]];
-    PT_HIP(hipDeviceSynchronize());
-    PT_HIP(hipMemcpy(out, U.states, sizeof(uint64_t) * (size_t)U.threads, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-// per-universe cycle counters of the fast kernel (clock64 around its phases), off by default
-extern "C" int pt_universe_set_profiling(pt_universe_set *set, int32_t on) {
-    PT_CHECK(set, PT_EINVAL, "null universe set");
-    if (on && !set->prof && !set->host.empty()) {
-        PT_HIP(hipMalloc((void **)&set->prof, 512 * set->host.size()));
-        PT_HIP(hipMemset(set->prof, 0, 512 * set->host.size()));
-    }
-    for (size_t i = 0; i < set->host.size(); ++i) set->host[i].prof = on && set->prof ? set->prof + 64 * i : nullptr;
-    return PT_OK;
-}
-
-// diagnostics: per universe (set order) 64 words: cycles in presampling / phase A / phase B, steps, batch size,
-// dim, entities, start / duration (100 MHz wall clock) of the last train call with profiling on; team universes: word
-// 60 (team width << 32 | one XCD), word 61 the cycles in team barriers; word 62 the rows
-// updated in phase B summed over the steps; the other words 8-63 phase stamps of one step (tuning build)
-extern "C" int pt_universe_set_profile(pt_universe_set *set, uint64_t *out) {
-    PT_CHECK(set && out, PT_EINVAL, "null argument");
-    PT_CHECK(set->prof, PT_ESTATE, "profiling not enabled (pt_universe_set_profiling)");
-    PT_HIP(hipDeviceSynchronize());
-    PT_HIP(hipMemcpy(out, set->prof, 512 * set->host.size(), hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-extern "C" int pt_universe_set_free(pt_universe_set *set) {
-    if (set) (void)hipDeviceSynchronize();
-    delete set;
-    return PT_OK;
-}
-
-extern "C" int pt_universes_train_ex(const pt_universe_job *jobs, int64_t n, int32_t model, int32_t p_norm,
-                                     int32_t norm_flag, int32_t opt, int64_t bern, int64_t filter, int32_t flags,
-                                     float *d_losses, void *stream) {
-    PT_CHECK((flags & ~PT_DETERMINISTIC) == 0, PT_EINVAL, "pt_universes_train_ex: unknown flags");
-    pt_universe_set *set = nullptr;
-    int rc = pt_universe_set_create(jobs, n, model, p_norm, norm_flag, opt, bern, filter, &set);
-    if (rc) return rc;
-    if (flags & PT_DETERMINISTIC) rc = pt_universe_set_deterministic(set, 1);
-    if (!rc) rc = pt_universe_set_train(set, d_losses, stream);
-    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    pt_universe_set_free(set);
-    if (!rc && e != hipSuccess) rc = pt::fail(PT_EHIP, std::string("pt_universes_train: ") + hipGetErrorString(e));
-    return rc;
-}
-
 // initial universe tables, torch-CPU-generator-identical (torch_init.hip)
 extern "C" int pt_torch_init_tables(const pt_torch_init_job *jobs, int64_t n, void *stream) {
     PT_CHECK(n >= 0 && (jobs || n == 0), PT_EINVAL, "pt_torch_init_tables: null jobs");
@@ -1969,19 +1167,6 @@ extern "C" int pt_torch_init_tables(const pt_torch_init_job *jobs, int64_t n, vo
     if (e == hipSuccess) e = f != hipSuccess ? f : w;
     if (e != hipSuccess) return pt::fail(PT_EHIP, std::string("pt_torch_init_tables: ") + hipGetErrorString(e));
     return PT_OK;
-}
-
-extern "C" int pt_universes_train(const pt_universe_job *jobs, int64_t n, int32_t model, int32_t p_norm,
-                                  int32_t norm_flag, int32_t opt, int64_t bern, int64_t filter, float *d_losses,
-                                  void *stream) {
-    pt_universe_set *set = nullptr;
-    int rc = pt_universe_set_create(jobs, n, model, p_norm, norm_flag, opt, bern, filter, &set);
-    if (rc) return rc;
-    rc = pt_universe_set_train(set, d_losses, stream);
-    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    pt_universe_set_free(set);
-    if (!rc && e != hipSuccess) rc = pt::fail(PT_EHIP, std::string("pt_universes_train: ") + hipGetErrorString(e));
-    return rc;
 }
 
 // ======================================================================== link prediction =======

@@ -26,16 +26,6 @@ struct UniverseDev {
     int32_t shape;                                  // universe_shape_id(dim)
 };
 
-// A team universe's exchange state (universes_team.h), beside its UniverseDev (kept apart: the class kernels hold
-// a register copy of their descriptor, whose size their SGPR spills follow)
-struct TeamDev {
-    float *part;                                    // [w][rel][dim] relation partials, [w][epochs] loss partials,
-                                                    // [w] the members' XCD ids
-    uint32_t *sync;                                 // arrival counter (zeroed before each launch)
-    uint32_t *err;                                  // the set's error word (a bounded poll ran out)
-    int32_t w;                                      // members
-};
-
 // workgroup size of each (model, shape class) kernel. TransE's narrow classes (<= 8 floats per lane) run 1,024
 // threads (16 waves, 4 per SIMD, 128 VGPRs: twice the lane groups, so a step's positives take half the rounds
 // and twice the waves hide each other's latency; measured C3 57.4 -> 52.5 ms, its longest universe 135 -> 100
@@ -52,11 +42,8 @@ constexpr int universe_class_threads(int model, int cls) { return model == 0 && 
 #endif
 constexpr int universe_hot_threads(int G) { return G >= 32 ? PT_UNI_HOT_WIDE_NT : PT_UNI_NT; }
 // class ids from kUniHotBase on: a "hot" class-1 shape (id - kUniHotBase) run by a kernel compiled for that shape
-// alone (its own register allocation; see pt_universe_set_create)
+// alone (its own register allocation; see choose_classes, universe_set.cpp)
 constexpr int kUniHotBase = 64;
-// class ids from kUniTeamBase on: universes of shape (id - kUniTeamBase) trained by teams of workgroups
-// (universes_team.h), one launch per shape
-constexpr int kUniTeamBase = 128;
 
 // launch configuration of one group of universes (host-chosen for the largest universe of the group)
 struct UniverseLaunch {
@@ -90,14 +77,6 @@ hipError_t launch_universes(const UniverseDev *d_us, int64_t n, int *counter, in
                             int p_norm, int norm_flag, int opt, int64_t neg, int bern, int filter,
                             const UniverseLaunch &cfg, hipStream_t st);
 int universe_shape_class(int shape);
-// team universes (universes_team.h): whether a shape has a team kernel (TransE, 8-float class), the dynamic LDS of
-// its launch, and the launch over `grid` workgroups (map: [grid][2] universe index into d_us, member or -1)
-bool universe_team_shape(int shape, int model);
-int64_t universe_team_lds_bytes(int64_t list_cap, int64_t rel, int64_t ent, int64_t slots, int64_t pchunk,
-                                int64_t seq, int64_t rel_step, int64_t dim);
-hipError_t launch_universes_team(const UniverseDev *d_us, const TeamDev *d_teams, const int32_t *d_map, int64_t grid,
-                                 int shape, int p_norm, int norm_flag, int opt, int64_t neg, int bern, int filter,
-                                 const UniverseLaunch &cfg, hipStream_t st);
 int universe_shape_groups(int shape, int model);
 int universe_shape_row_slots(int shape);
 

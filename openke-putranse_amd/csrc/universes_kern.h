@@ -272,20 +272,7 @@ struct UniverseSink {
 // per-negative row-role bookkeeping). get_neg(q, k, &e, &tail_side). Gradients in normalized space, like
 // group_step for TransE; a corrupted row equal to a positive row is simply a separate contribution.
 // Positive q's gradient rows go to sink sk[q] (its own contribution slots). Returns the summed losses.
-// Row of a universe table for transe_step: SC1 (a team universe, universes_team.h) loads it past the CU's L1 with
-// sc1 buffer loads (rows another team member updated), else uload.
-template <bool SC1, int G, int VEC, int KCH>
-__device__ __forceinline__ void trow(V<G, VEC, KCH> &o, const float *table, int64_t rows, int row, int D, int lane) {
-    if constexpr (SC1)
-        bload<G, VEC, KCH, 16>(o, make_rsrc(table, (uint32_t)(rows * D * 4)), (uint32_t)(row * D * 4), D, lane);
-    else
-        uload(o, table + row * D, D, lane);
-}
-
-// ALWAYS (team universes): every row of the positive goes to its sink, a zero row for an inactive pair, so each
-// positive fills its static contribution slots (neg negatives, relation, head, tail) whatever its margin decisions.
-template <int NP, int G, int VEC, int KCH, bool PF = false, bool ALWAYS = false, bool SC1 = false, typename Sink,
-          typename NegFn>
+template <int NP, int G, int VEC, int KCH, bool PF = false, typename Sink, typename NegFn>
 __device__ __forceinline__ float transe_step(const StepParams &P, const int (&hp)[NP], const int (&rp)[NP],
                                              const int (&tp)[NP], int neg, NegFn get_neg, const Sink (&sk)[NP],
                                              int lane) {
@@ -298,9 +285,9 @@ __device__ __forceinline__ float transe_step(const StepParams &P, const int (&hp
     Vec hh[NP], th[NP], rh[NP];
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
-        trow<SC1>(hh[q], P.ent, P.ent_total, hp[q], D, lane);
-        trow<SC1>(th[q], P.ent, P.ent_total, tp[q], D, lane);
-        trow<SC1>(rh[q], P.rel, P.rel_total, rp[q], D, lane);
+        uload(hh[q], P.ent + hp[q] * D, D, lane);
+        uload(th[q], P.ent + tp[q] * D, D, lane);
+        uload(rh[q], P.rel + rp[q] * D, D, lane);
     }
     // long wide rows (16 floats per lane over >= 16 lanes: TransE rows over 512 floats since r04): the first
     // negative's row loads with the positive's, the rest one at a time in the loop (measured r02 on C4's then
@@ -319,7 +306,7 @@ __device__ __forceinline__ float transe_step(const StepParams &P, const int (&hp
         tail_side[q] = false;
         if (kPrefetch && neg > 0) {
             get_neg(q, 0, e[q], tail_side[q]);
-            trow<SC1>(x[q], P.ent, P.ent_total, e[q], D, lane);
+            uload(x[q], P.ent + e[q] * D, D, lane);
         }
     }
     float ps[NP], csum[NP], lsum[NP];
@@ -351,7 +338,7 @@ __device__ __forceinline__ float transe_step(const StepParams &P, const int (&hp
 #pragma unroll
             for (int q = 0; q < NP; ++q) {
                 get_neg(q, k, e[q], tail_side[q]);
-                trow<SC1>(x[q], P.ent, P.ent_total, e[q], D, lane);
+                uload(x[q], P.ent + e[q] * D, D, lane);
             }
         }
 #pragma unroll
@@ -378,9 +365,6 @@ __device__ __forceinline__ float transe_step(const StepParams &P, const int (&hp
                 }
                 sk[q].ent(e[q], x[q], D, lane);   // corrupted tail gets -g, corrupted head +g
                 PT_USTAMP(sk[0].trace, 3);
-            } else if constexpr (ALWAYS) {
-                vzero(x[q]);
-                sk[q].ent(e[q], x[q], D, lane);
             }
         }
     }
@@ -411,10 +395,6 @@ __device__ __forceinline__ float transe_step(const StepParams &P, const int (&hp
             PT_USTAMP(sk[0].trace, 5);
             sk[q].ent(hp[q], aH[q], D, lane);
             PT_USTAMP(sk[0].trace, 6);
-            sk[q].ent(tp[q], aT[q], D, lane);
-        } else if constexpr (ALWAYS) {   // (no active pair: the accumulators are zero)
-            sk[q].rel(rp[q], aR, D, lane);
-            sk[q].ent(hp[q], aH[q], D, lane);
             sk[q].ent(tp[q], aT[q], D, lane);
         }
         loss += lsum[q];
@@ -634,7 +614,6 @@ struct UniShared {
     int *count, *ccount;
     float *loss;
     PreTables *pre;
-    int *rcount = nullptr;   // (team universes: the step's relation count)
 };
 
 // One universe's whole training run (all epochs x nbatches steps) by the calling workgroup.

@@ -731,41 +731,27 @@ def _small_set_cases(L, graph, kg, seed):
     return cases
 
 
-@pytest.mark.parametrize("width", [2, 4])
-def test_universe_teams_equal_one_workgroup_and_oracle(width):
-    """Team universes (universes_team.h; off by default since round 6 - measured slower than one workgroup): a set of
-    fewer universes than CUs trains its longest TransE universes with teams of `width` workgroups
-    (pt_universe_set_teams > 0). Under SGD with p = 2 (no noise amplification, no sign decisions), over whole runs of
-    3 epochs x 10 steps: the team-trained tables equal the one-workgroup tables and the oracle's trajectory within
-    5e-5, the sampler streams end where the oracle's do, the per-epoch losses agree within 1e-5; and under Adagrad
-    each team step equals the oracle's step from the same state (teacher forcing, test_universe_kernel_matches_oracle's
-    bound)."""
+def test_universe_set_sgd_runs_match_oracle():
+    """A set of six TransE universes (scalar and float4 row classes) trained twice from the same start. Under SGD with
+    p = 2 (no noise amplification, no sign decisions), over whole runs of 3 epochs x 10 steps: the two runs' tables
+    equal each other and the oracle's trajectory within 5e-5, the sampler streams end where the oracle's do, the
+    per-epoch losses agree within 1e-5; and under Adagrad each step equals the oracle's step from the same state
+    (teacher forcing, test_universe_kernel_matches_oracle's bound)."""
     import ctypes
     from openke import _native
     L = _native.lib()
     kg = oracle.KG.load(KG_SMALL)
     graph = ctypes.c_void_p()
     _native.check(L.pt_graph_load(KG_SMALL.encode(), ctypes.byref(graph)))
-    default_w = L.pt_get_universe_team_width()
-    cases = _small_set_cases(L, graph, kg, 31 + width)
+    cases = _small_set_cases(L, graph, kg, 31)
     try:
-        def teams(w):
-            def check(uset):
-                nt, nw = ctypes.c_int64(), ctypes.c_int64()
-                _native.check(L.pt_universe_set_teams(uset, ctypes.byref(nt), ctypes.byref(nw)))
-                if w > 1:
-                    assert nt.value > 0 and nw.value >= 2 * nt.value, (nt.value, nw.value)
-                else:
-                    assert nt.value == 0
-            return (lambda: _native.check(L.pt_set_universe_team_width(w))), check
-        _check_sgd_runs(cases, _sgd_set_runs(L, cases, [teams(width), teams(1)]))
-        # Adagrad, teacher-forced step by step with teams of `width`
-        _native.check(L.pt_set_universe_team_width(width))
+        plain = (lambda: None), (lambda uset: None)
+        _check_sgd_runs(cases, _sgd_set_runs(L, cases, [plain, plain]))
+        # Adagrad, teacher-forced step by step
         for c in cases:
             c["lr"], c["epochs"], c["nbatches"] = 0.05, 1, 6
         _teacher_forced_universes(L, cases, "TransE", 1, "adagrad", 1, 0, 0)
     finally:
-        _native.check(L.pt_set_universe_team_width(default_w))
         for c in cases:
             L.pt_universe_free(c["h"])
         L.pt_graph_free(graph)

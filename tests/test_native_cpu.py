@@ -369,3 +369,18 @@ def test_universe_dims_supported():
     for d in range(516, 1025, 4):
         assert L.pt_universe_dim_supported(d, _native.PT_TRANSE) == 1, d
     assert L.pt_universe_dim_supported(0, _native.PT_TRANSE) == 0
+
+
+def test_universe_team_width_shim():
+    """Team universes were removed; pt_set_universe_team_width stays as a compatibility shim: width 1 (one workgroup
+    per universe, what every set trains with) is accepted, any other width is PT_ENOTSUP (6) with a message that
+    says so, and the getter stays at 1."""
+    from openke import _native
+    L = _native.lib()
+    assert L.pt_set_universe_team_width(1) == 0
+    assert L.pt_get_universe_team_width() == 1
+    for w in (2, 4):
+        assert L.pt_set_universe_team_width(w) == 6, w
+        msg = L.pt_last_error().decode()
+        assert "removed" in msg and "DESIGN" in msg, msg
+        assert L.pt_get_universe_team_width() == 1

@@ -6,7 +6,8 @@ set -u
 export RESULTS=${RESULTS:-results}   # where this script leaves its logs and summaries
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 W=${W:-c4}
-TW=${TW:-1}   # team width (1: the product's one-workgroup chain, which bench.py's roofline uses)
+TW=${TW:-1}   # team width: only 1 (one workgroup per universe) since the team trainer was removed; the library
+              # answers any other width with PT_ENOTSUP
 D=$RESULTS/pmcc_${W}_w$TW
 mkdir -p $D
 timeout -s KILL 120 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD \
