@@ -313,6 +313,9 @@ int pt_lp_min_scores(const pt_lp_universe *us, int64_t n_universes, int32_t mode
 /* d_key_tuple (optional, [n_keys], init +inf): MIN over the pairs' universes of the null_vector score
  * _calc(anchor, 0, r) / _calc(0, anchor, r) on the raw anchor row (calc_tuple_score,
  * Parallel_Universe_Config.py:405-416, transmit_tuple_max_score :494-514) */
+/* Keys per batch of pt_lp_min_scores at this global_ent_total (read-only; no device call): the call scores keys
+ * [b * n, (b + 1) * n) in jobs of their own, so that a batch's score rows stay cache resident. */
+int64_t pt_lp_keys_per_batch(int64_t global_ent_total);
 
 /* Ranks straight from global-order score rows (device): query q is ranked on row d_row_of[q] with
  * truth entity d_truth[q]; +inf entries are replaced by d_repl[q] when d_repl is non-NULL

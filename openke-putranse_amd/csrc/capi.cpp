@@ -1170,6 +1170,15 @@ extern "C" int pt_torch_init_tables(const pt_torch_init_job *jobs, int64_t n, vo
 }
 
 // ======================================================================== link prediction =======
+// keys of one batch of pt_lp_min_scores: as many score rows (global_ent_total floats each) as fit the batch
+// budget (PT_LP_BATCH_MB in the tuning build, default 192), at least one
+static int64_t lp_keys_per_batch(int64_t global_ent_total) {
+    int64_t batch_mb = 192;
+    if (const char *v = pt_tuning_env("PT_LP_BATCH_MB")) batch_mb = std::max<int64_t>(1, atoll(v));
+    return std::max<int64_t>(1, (batch_mb << 20) / (4 * std::max<int64_t>(global_ent_total, 1)));
+}
+extern "C" int64_t pt_lp_keys_per_batch(int64_t global_ent_total) { return lp_keys_per_batch(global_ent_total); }
+
 extern "C" int pt_lp_min_scores(const pt_lp_universe *us, int64_t n_universes, int32_t model, int32_t p_norm,
                                 int32_t norm_flag, const pt_lp_pair *pairs, int64_t n_pairs,
                                 int64_t global_ent_total, float *d_key_rows, float *d_key_tuple, void *stream) {
@@ -1201,10 +1210,7 @@ extern "C" int pt_lp_min_scores(const pt_lp_universe *us, int64_t n_universes, i
     // sorted by universe so each universe's entity rows are read once per job.
     int64_t n_keys = 0;
     for (int64_t i = 0; i < n_pairs; ++i) n_keys = std::max<int64_t>(n_keys, (int64_t)pairs[i].key + 1);
-    int64_t batch_mb = 192;
-    if (const char *v = pt_tuning_env("PT_LP_BATCH_MB")) batch_mb = std::max<int64_t>(1, atoll(v));
-    const int64_t keys_per_batch =
-        std::max<int64_t>(1, (batch_mb << 20) / (4 * std::max<int64_t>(global_ent_total, 1)));
+    const int64_t keys_per_batch = lp_keys_per_batch(global_ent_total);
     const int64_t n_batches = (n_keys + keys_per_batch - 1) / keys_per_batch;
     // jobs ordered by (shape key, batch); the pairs of a (job, universe) keep their input order: a counting sort
     // over (job, universe) in place of per-job per-universe vectors (2 M pairs for C4)

@@ -135,6 +135,7 @@ SIGNATURES = {
                                              c_i64, c_i32, c_vp, c_vp]),
     "pt_lp_min_scores": (ctypes.c_int, [ctypes.POINTER(LpUniverse), c_i64, c_i32, c_i32, c_i32,
                                         ctypes.POINTER(LpPair), c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "pt_lp_keys_per_batch": (c_i64, [c_i64]),
     "pt_rank_rows": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "pt_rank_types": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
                                      c_vp, c_vp]),

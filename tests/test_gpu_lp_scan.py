@@ -7,8 +7,9 @@ Until round 6 the compiler's fp contraction fused some of those loops' products 
 same pair's score could differ by an ulp between the two paths. Every rounding is now explicit (x-hat = x * inv
 from the sum8 tree of fma squares; y = fma(sg, x-hat, b); |y| added, or fma(y, y, a); dim d into partial d mod 8),
 and a pair's score must not depend on the path: the rows of one call over all pairs equal, bit for bit, those of
-one call per pair (a universe with one pair takes the one-pair path). The rows of both are checked against the
-oracle's scores elsewhere (test_gpu_pu, test_gpu_configs C4, test_gpu_realscale)."""
+one call per pair (a universe with one pair takes the one-pair path). This file compares the kernel with itself
+only; the values are held to a float64 reference, cell by cell, in test_gpu_lp_values.py (test_gpu_pu,
+test_gpu_configs C4 and test_gpu_realscale compare ranks, which forgive near-ties)."""
 import ctypes
 
 import numpy as np
