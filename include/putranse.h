@@ -141,21 +141,18 @@ int pt_trainer_run_timed(pt_trainer *t, pt_sampler *sampler, int64_t bs, int64_t
  * k_sample_csr + k_scan_counts; PT_PATH_SAMPLED: none (small neg: the step kernel samples). -1 before any. */
 enum { PT_PATH_TWO_PASS = 0, PT_PATH_FUSED = 1, PT_PATH_PART = 2, PT_PATH_SAMPLED = 3 };
 int pt_trainer_last_path(const pt_trainer *t);
-/* The large-neg TransE step as ONE launch that also updates the table rows (step_apply.hip: each row
- * updated inside the step by the wave delivering its last gradient contribution, same operations and
- * order as the separate apply pass), for float4 rows of 33-256 chunks (dim 132-1024, dim % 4 == 0);
- * on = 0 keeps the step + apply pair. Default off (measured slower at C2: DESIGN.md section 4). Results
- * equal the pair's up to float-atomic order. */
+/* SHIM of a removed opt-in mode, the one-launch fused step + apply of the large-neg TransE step (measured slower
+ * than the step + apply pair and removed: DESIGN.md section 4), kept so that callers which switch it off or ask
+ * whether it ran keep working. The setter accepts on = 0 (PT_OK) and answers PT_ENOTSUP to anything else (PT_EINVAL
+ * for a null trainer); the getter returns 0. */
 int pt_trainer_set_step_apply(pt_trainer *t, int32_t on);
+int pt_trainer_step_apply(const pt_trainer *t);
 /* slot-scale mode (opt-in; TransE float4 rows on the counting-sort path): the step stores per (positive, negative)
  * slot a record (positive, side, one scalar) and per positive its three normalized rows instead of the corrupted
  * entity's gradient row, and the apply pass re-forms each slot's row from them and the entity's own row
  * (CsrWork::slot_scale). pt_trainer_slot_scale: 1 when the current workspace is carved for it. */
 int pt_trainer_set_slot_scale(pt_trainer *t, int32_t on);
 int pt_trainer_slot_scale(const pt_trainer *t);
-/* whether the last enqueued in-kernel-sampled steps took the fused step + apply (ms4[2] of
- * pt_trainer_run_timed is then that kernel, ms4[3] the chunks' loss reduction) */
-int pt_trainer_step_apply(const pt_trainer *t);
 /* Sample `calls` consecutive steps into the counting-sort batch layout the large-neg step kernels read,
  * by path `path` (PT_PATH_FUSED / PT_PATH_PART / PT_PATH_TWO_PASS, or -1 = the automatic choice), advance
  * the sampler streams, and copy the batches to HOST arrays (synchronizes): h_pos [calls][bs][3] (h, r, t

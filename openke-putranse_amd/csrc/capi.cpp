@@ -1,16 +1,15 @@
 // C-ABI of libputranse_hip.so (include/putranse.h): reentrant pt_* entry points and the reference's
 // Base.so symbols for the hot path, all executing batch construction / training / scoring on the GPU.
-// (The universe-set runtime, pt_universe_set_* and pt_universes_train, is universe_set.cpp.)
+// (The trainer runtime, pt_trainer_*, is trainer.cpp; the universe-set runtime, pt_universe_set_* and
+// pt_universes_train, is universe_set.cpp.)
 #include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <thread>
-#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -20,7 +19,7 @@
 #include "kernels.h"
 #include "ordered.h"
 #include "rng.h"
-#include "step_apply.h"
+#include "trainer.h"
 #include "universe.h"
 #include "universes.h"
 
@@ -39,85 +38,8 @@ int fail(int code, const std::string &msg) {
 extern "C" const char *pt_last_error(void) { return pt::g_err.c_str(); }
 extern "C" int pt_version(void) { return 1; }
 
-// ======================================================================== objects ================
-struct pt_sampler {
-    pt::Graph *g = nullptr;        // graph sampled from (follows swaps for the legacy context)
-    int64_t threads = 0;
-    uint64_t *d_states = nullptr;  // device LCG states, one per emulated sampler thread
-    int device = -1;
-    ~pt_sampler() {
-        if (d_states) (void)hipFree(d_states);
-    }
-};
-
-struct GraphKey {
-    const void *sampler, *graph, *losses, *states;
-    int64_t bs, neg, bern, filter, steps;
-    bool operator<(const GraphKey &o) const {
-        return std::tie(sampler, graph, losses, states, bs, neg, bern, filter, steps) <
-               std::tie(o.sampler, o.graph, o.losses, o.states, o.bs, o.neg, o.bern, o.filter, o.steps);
-    }
-};
-
-struct pt_trainer {
-    pt::StepParams P{};
-    pt::StepWorkspace W{};
-    void *ws_block = nullptr;
-    size_t ws_bytes = 0;   // gradient rows + touched flags (all zero between steps)
-    // counting-sort gradient path for large neg (allocated on first use, grown as needed)
-    void *csr_block = nullptr;
-    size_t csr_cap = 0;
-    pt::CsrWork csr{};
-    int64_t csr_bs = 0, csr_neg = 0, csr_chunk = 0;   // layout the workspace was carved for
-    bool csr_fused = false;                             // k_sample_sort plan fits LDS
-    // the fused step + apply (step_apply.hip) for TransE with 33-256 float4 chunks per row: its rows and
-    // arrival words live in the counting-sort workspace (fr.gent == nullptr: not carved for it)
-    pt::FusedRows fr{};
-    bool step_apply_on = false;                         // pt_trainer_set_step_apply (opt-in: measured slower)
-    bool slot_scale_on = false;                         // pt_trainer_set_slot_scale (CsrWork::slot_scale)
-    bool last_step_apply = false;                       // the last enqueued in-kernel-sampled steps took it
-    bool csr_part = false;                              // k_sample_part prepared (its LDS limit raised)
-    int last_path = -1;                                 // sampling path of the last enqueued chunk (PT_PATH_*)
-    int64_t lpart_cap = 0;                             // W.lpart capacity (positives)
-    int device = -1;
-    hipStream_t cap = nullptr;
-    // the split sampler's second launch of a chunk (sample_split_head): its stream and the fork / join events
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int64_t split_override = -1;                        // pt_trainer_set_sample_split: head steps, 0 off, -1 auto
-    std::map<GraphKey, hipGraphExec_t> graphs;
-    int path_override = -1;                             // pt_trainer_set_sampling: PT_PATH_* or -1 (automatic)
-    int64_t parts_override = 0;                         // split-sampler workgroups per call (0: automatic)
-    int64_t prof_calls = 0, prof_parts = 0, prof_cap = 0;   // PT_PART_PROF (tuning build) record layout
-    // reference-order (deterministic) mode: ordered.hip's step on k_sample batches (pt_trainer_set_deterministic)
-    bool ordered = false;
-    void *ord_block = nullptr;
-    size_t ord_cap = 0;
-    int64_t *ord_h = nullptr, *ord_t = nullptr, *ord_r = nullptr;
-    float *ord_y = nullptr, *ord_score = nullptr, *ord_ds = nullptr;
-    float *ord_g = nullptr;   // [4][seq][dim] per-slot gradient rows
-    void drop_graphs() {
-        for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
-        graphs.clear();
-    }
-    ~pt_trainer() {
-        drop_graphs();
-        if (cap) (void)hipStreamDestroy(cap);
-        if (side) (void)hipStreamDestroy(side);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (ev_join) (void)hipEventDestroy(ev_join);
-
-        if (ws_block) (void)hipFree(ws_block);
-        if (csr_block) (void)hipFree(csr_block);
-        if (csr.prof) (void)hipFree(csr.prof);
-        if (W.lpart) (void)hipFree(W.lpart);
-        if (ord_block) (void)hipFree(ord_block);
-    }
-};
-
-namespace {
-
-int desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
+// ======================================================================== model descriptor =======
+int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
     PT_CHECK(m, PT_EINVAL, "null model descriptor");
     PT_CHECK(m->model == PT_TRANSE || m->model == PT_TRANSH, PT_EINVAL, "model must be PT_TRANSE or PT_TRANSH");
     PT_CHECK(m->p_norm == 1 || m->p_norm == 2, PT_ENOTSUP, "p_norm must be 1 or 2");
@@ -141,31 +63,6 @@ int desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
     if (const char *v = pt_tuning_env("PT_STEP_DBG")) P.dbg = atoi(v);
     return PT_OK;
 }
-
-// negatives at or above this count take the counting-sort path (PT_CSR=0/1 overrides)
-bool use_csr(int64_t neg) {
-    static int forced = [] {
-        const char *v = pt_tuning_env("PT_CSR");
-        return v ? atoi(v) : -1;
-    }();
-    return forced >= 0 ? forced != 0 : neg >= 4;
-}
-
-int check_step_args(const pt::StepParams &P, pt_sampler *s, int64_t bs, int64_t neg, const int64_t *bh) {
-    PT_CHECK(bs > 0 && neg > 0, PT_EINVAL, "batch_size and neg_ent must be positive");
-    if (!bh) {
-        PT_CHECK(s && s->g && s->d_states, PT_ESTATE, "in-kernel sampling needs a sampler bound to a graph");
-        PT_CHECK(s->g->ent_total <= P.ent_total && s->g->rel_total <= P.rel_total, PT_EINVAL,
-                 "graph ids exceed the model tables");
-        PT_CHECK(s->g->ent_total > 1, PT_EINVAL, "graph needs at least two entities");
-        pt::StepParams Q = P;
-        Q.batch_size = bs;
-        PT_CHECK(pt::step_fits(Q, neg, use_csr(neg)), PT_ENOTSUP, "neg_ent too large for the LDS draw buffer");
-    }
-    return PT_OK;
-}
-
-}  // namespace
 
 // ======================================================================== graphs =================
 // Opt-in count-header record format for every *2id.txt reader (pt_graph_load, importTrainFiles,
@@ -205,7 +102,7 @@ extern "C" int pt_graph_triples(const pt_graph *g, int64_t *h, int64_t *t, int64
 }
 
 // ======================================================================== sampler ================
-static int sampler_init(pt_sampler *s, pt::Graph *g, int64_t threads, const uint64_t *seeds) {
+int pt::sampler_init(pt_sampler *s, pt::Graph *g, int64_t threads, const uint64_t *seeds) {
     PT_CHECK(threads > 0 && threads <= 64, PT_ENOTSUP, "threads must be in [1, 64]");
     PT_HIP(hipGetDevice(&s->device));
     s->g = g;
@@ -223,7 +120,7 @@ static int sampler_init(pt_sampler *s, pt::Graph *g, int64_t threads, const uint
 extern "C" int pt_sampler_create(pt_graph *g, int64_t threads, const uint64_t *seeds, pt_sampler **out) {
     PT_CHECK(g && out && seeds, PT_EINVAL, "pt_sampler_create: null argument");
     auto *s = new pt_sampler();
-    int rc = sampler_init(s, &g->g, threads, seeds);
+    int rc = pt::sampler_init(s, &g->g, threads, seeds);
     if (rc) {
         delete s;
         return rc;
@@ -268,764 +165,13 @@ extern "C" int pt_sampler_sample(pt_sampler *s, int64_t bs, int64_t neg, int64_t
     return pt_sampler_sample_ex(s, bs, neg, 0, 0, bern, filter, d_h, d_t, d_r, d_y, stream);
 }
 
-// ======================================================================== training ===============
-extern "C" int pt_trainer_create(const pt_model_desc *m, pt_trainer **out) {
-    PT_CHECK(out, PT_EINVAL, "pt_trainer_create: null argument");
-    auto t = std::make_unique<pt_trainer>();
-    int rc = desc_to_params(m, t->P);
-    if (rc) return rc;
-    PT_HIP(hipGetDevice(&t->device));
-    const int64_t E = t->P.ent_total, R = t->P.rel_total, D = t->P.dim;
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t ge = al(4 * E * D), gr = al(4 * R * D), gn = m->model == PT_TRANSH ? al(4 * R * D) : 0;
-    const size_t fe = al(4 * E), fr = al(4 * R), fn = m->model == PT_TRANSH ? al(4 * R) : 0;
-    const size_t total = ge + gr + gn + fe + fr + fn;
-    PT_HIP(hipMalloc(&t->ws_block, total));
-    PT_HIP(hipMemset(t->ws_block, 0, total));
-    t->ws_bytes = total;
-    char *b = (char *)t->ws_block;
-    t->W.gent = (float *)b; b += ge;
-    t->W.grel = (float *)b; b += gr;
-    t->W.gnorm = gn ? (float *)b : nullptr; b += gn;
-    t->W.fent = (int *)b; b += fe;
-    t->W.frel = (int *)b; b += fr;
-    t->W.fnorm = fn ? (int *)b : nullptr;
-    PT_HIP(hipStreamCreateWithFlags(&t->cap, hipStreamNonBlocking));
-    PT_HIP(hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking));
-    PT_HIP(hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming));
-    PT_HIP(hipEventCreateWithFlags(&t->ev_join, hipEventDisableTiming));
-    *out = t.release();
-    return PT_OK;
-}
-extern "C" int pt_trainer_free(pt_trainer *t) {
-    delete t;
-    return PT_OK;
-}
-extern "C" int pt_trainer_update_desc(pt_trainer *t, const pt_model_desc *m) {
-    PT_CHECK(t, PT_EINVAL, "null trainer");
-    pt::StepParams P{};
-    int rc = desc_to_params(m, P);
-    if (rc) return rc;
-    PT_CHECK(P.model == t->P.model && P.ent_total <= t->P.ent_total && P.rel_total <= t->P.rel_total &&
-                 P.dim == t->P.dim,
-             PT_EINVAL, "descriptor shape differs from the trainer's workspace");
-    t->P = P;
-    t->drop_graphs();
-    return PT_OK;
-}
-
-
-static const int64_t kCsrChunk = 256;   // steps pre-sampled per sampling/scan launch pair
-// the fused sampling kernel runs one workgroup per call (~200 us each at C2, latency-bound draws), so it
-// only beats the split form once a chunk fills enough CUs on its own
-static const int64_t kSampleSortMinCalls = 96;
-// the split sampler (k_sample_part) runs ceil(kPartTarget / calls) workgroups per call
-static const int64_t kPartTarget = 512;
-
-// Sampling path for a chunk of `calls` steps: pt_trainer_set_sampling forces one (where its plan fits;
-// the tuning build also reads PT_SAMPLE_MODE = fused | part | twopass and PT_SAMPLE_TWO_PASS=1); by default
-// the fused kernel for chunks of >= kSampleSortMinCalls steps, the split sampler below that.
-static int sample_mode(const pt_trainer *t) {
-    if (t->path_override >= 0) return t->path_override;
-    const char *tp = pt_tuning_env("PT_SAMPLE_TWO_PASS");
-    if (tp && atoi(tp) != 0) return PT_PATH_TWO_PASS;
-    const char *v = pt_tuning_env("PT_SAMPLE_MODE");
-    if (!v) return -1;
-    if (!strcmp(v, "fused")) return PT_PATH_FUSED;
-    if (!strcmp(v, "part")) return PT_PATH_PART;
-    if (!strcmp(v, "twopass")) return PT_PATH_TWO_PASS;
-    return -1;
-}
-static int64_t part_count(const pt_trainer *t, int64_t calls, int64_t bs) {
-    int64_t p = (kPartTarget + calls - 1) / calls;
-    if (t->parts_override > 0) p = t->parts_override;
-    else if (const char *v = pt_tuning_env("PT_PART_COUNT")) p = atoll(v);
-    if (p < 2) p = 2;
-    return p > bs ? bs : p;
-}
-static int choose_path(const pt_trainer *t, int64_t calls, int64_t bs, int64_t neg, int forced) {
-    const bool part_ok = t->csr_part && pt::sample_part_fits(bs, neg, t->P.ent_total, part_count(t, calls, bs));
-    if (forced == PT_PATH_FUSED && t->csr_fused) return PT_PATH_FUSED;
-    if (forced == PT_PATH_PART && part_ok) return PT_PATH_PART;
-    if (forced == PT_PATH_TWO_PASS) return PT_PATH_TWO_PASS;
-    if (t->csr_fused && calls >= kSampleSortMinCalls) return PT_PATH_FUSED;
-    if (part_ok) return PT_PATH_PART;
-    return PT_PATH_TWO_PASS;
-}
-
-// whether the fused step + apply is wanted for this trainer (opt-in, pt_trainer_set_step_apply; the tuning build's
-// PT_STEP_APPLY=0 vetoes it): only then does ensure_csr carve its extra state
-static bool step_apply_wanted(const pt_trainer *t) {
-    static const int forced = [] {
-        const char *v = pt_tuning_env("PT_STEP_APPLY");
-        return v ? atoi(v) : -1;
-    }();
-    return t->step_apply_on && forced != 0;
-}
-
-// whether the slot-scale mode is wanted (pt_trainer_set_slot_scale; the tuning build's PT_SLOT_SCALE forces it)
-static bool slot_scale_wanted(const pt_trainer *t) {
-    static const int forced = [] {
-        const char *v = pt_tuning_env("PT_SLOT_SCALE");
-        return v ? atoi(v) : -1;
-    }();
-    return forced >= 0 ? forced != 0 : t->slot_scale_on;
-}
-
-// Workspace of the counting-sort path, carved once per (bs, neg): room for a chunk of pre-sampled
-// steps (<= kCsrChunk, fewer when a step's arrays are large) plus one step's gradient rows. A new
-// (bs, neg) re-carves it (and drops captured graphs, whose kernels hold the old pointers).
-static int ensure_csr(pt_trainer *t, int64_t bs, int64_t neg) {
-    if (t->csr_block && t->csr_bs == bs && t->csr_neg == neg) return PT_OK;
-    const int64_t E = t->P.ent_total, R = t->P.rel_total, D = t->P.dim;
-    const int64_t cs = (E + 3) & ~int64_t(3), ss = (E + 4) & ~int64_t(3);
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    // the fused step + apply's extra state: per call the rows' uses and the loss partials; padded gradient
-    // rows and arrival words; contribution rows at the padded stride
-    pt::StepParams Q = t->P;
-    Q.batch_size = bs;
-    Q.neg = neg;
-    const bool sa = step_apply_wanted(t) && pt::step_apply_supported(Q, bs, neg);
-    const int64_t dp = sa ? pt::step_apply_row_stride(D) : D, us = (E + R + 63) & ~int64_t(63);
-    const size_t per_call = 16 * bs + 8 * bs * neg + 4 * cs + 4 * ss + 4 + 1024 + (sa ? 4 * us + 4 * bs : 0);
-    int64_t chunk = (int64_t)std::max<size_t>(1, ((size_t)512 << 20) / per_call);
-    chunk = std::min(chunk, kCsrChunk);
-    const size_t a_use = sa ? al(4 * us * chunk) : 0, a_lp = sa ? al(4 * bs * chunk) : 0,
-                 a_gent = sa ? al(4 * E * dp) : 0, a_grel = sa ? al(4 * R * dp) : 0, a_arr = sa ? al(8 * (E + R)) : 0;
-    // slot-scale mode: the step's slot records and positive base rows take the contribution region's place
-    // (TransE float4 rows: the k_step_csr / k_apply_buf pair; not with the fused step + apply)
-    const bool scm = slot_scale_wanted(t) && !sa && t->P.model == 0 && D % 4 == 0;
-    const size_t a_srec = al(8 * bs * neg), a_bases = al(4 * bs * 3 * D);
-    const size_t a_pos = al(16 * bs * chunk), a_neg = al(4 * bs * neg * chunk), a_off = a_neg,
-                 a_cnt = al(4 * cs * chunk), a_start = al(4 * ss * chunk), a_tick = al(4 * chunk + 4),
-                 a_con = std::max(al(4 * bs * neg * dp), scm ? a_srec + a_bases : (size_t)0);
-    const size_t need = a_use + a_lp + a_gent + a_grel + a_arr + a_pos + a_neg + a_off + a_cnt + a_start + a_tick + a_con;
-    PT_HIP(hipDeviceSynchronize());   // queued work may still use the old carving
-    t->drop_graphs();
-    if (need > t->csr_cap) {
-        if (t->csr_block) (void)hipFree(t->csr_block);
-        t->csr_block = nullptr;
-        t->csr_cap = 0;
-        PT_HIP(hipMalloc(&t->csr_block, need));
-        t->csr_cap = need;
-    }
-    PT_HIP(hipMemset(t->csr_block, 0, need));   // bucket counts start at zero; the scan re-zeroes them
-    char *b = (char *)t->csr_block;
-    // the per-chunk memset's block (row uses) first, at the allocation's start
-    t->csr.uses = sa ? (int32_t *)b : nullptr; b += a_use;
-    t->csr.use_stride = us;
-    t->csr.rel_base = E;
-    t->csr.lpart = sa ? (float *)b : nullptr; b += a_lp;
-    t->fr.gent = sa ? (float *)b : nullptr; b += a_gent;
-    t->fr.grel = sa ? (float *)b : nullptr; b += a_grel;
-    t->fr.arrive = sa ? (uint64_t *)b : nullptr; b += a_arr;
-    t->fr.dp = (int32_t)dp;
-    t->csr.pos = (int4 *)b; b += a_pos;
-    t->csr.neg = (int32_t *)b; b += a_neg;
-    t->csr.off = (int32_t *)b; b += a_off;
-    t->csr.cnt = (int32_t *)b; b += a_cnt;
-    t->csr.start = (int32_t *)b; b += a_start;
-    t->csr.tick = (int32_t *)b; b += a_tick;
-    t->csr.contrib = (float *)b;
-    t->csr.slot_scale = scm ? 1 : 0;
-    t->csr.srec = scm ? (int2 *)b : nullptr;
-    t->csr.bases = scm ? (float *)(b + a_srec) : nullptr;
-    t->csr.cnt_stride = cs;
-    t->csr.start_stride = ss;
-    t->csr_bs = bs;
-    t->csr_neg = neg;
-    t->csr_chunk = chunk;
-    // sampling + counting sort in LDS (one workgroup per call, or split over parts) when the plans fit
-    // (sets the kernels' LDS attributes here, outside any stream capture)
-    t->csr_fused = pt::sample_sort_prepare(bs, neg, E, ss);
-    t->csr_part = pt::sample_part_prepare(bs, neg, E, std::min<int64_t>(bs, kPartTarget));
-    if (const char *dd = pt_tuning_env("PT_PART_DBG")) t->csr.dbg = atoi(dd);
-    // PT_PART_PROF=1: phase timestamps of the split sampler (reported by pt_trainer_run_timed)
-    if (const char *pp = pt_tuning_env("PT_PART_PROF")) {
-        if (atoi(pp) != 0 && !t->csr.prof) {
-            t->prof_cap = kCsrChunk * 1024;   // (call, part) records
-            PT_HIP(hipMalloc(&t->csr.prof, sizeof(uint64_t) * 8 * (size_t)t->prof_cap));
-        }
-    }
-    return PT_OK;
-}
-
-// Launch recorder for the measurement hook: an event pair around every launch, by kernel kind
-// (0 sampling, 1 bucket scan, 2 forward/backward, 3 optimizer apply).
-struct Timing {
-    // events created up front (hipEventCreate between launches would stall the enqueue and let the
-    // GPU idle inside a measured interval)
-    std::vector<hipEvent_t> pool;
-    size_t used = 0;
-    std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> ev;
-    int reserve(size_t n) {
-        pool.resize(n);
-        for (auto &e : pool) PT_HIP(hipEventCreate(&e));
-        return PT_OK;
-    }
-    int begin(int kind, hipStream_t st, hipEvent_t *a) {
-        if (used >= pool.size()) return pt::fail(PT_EHIP, "timing event pool exhausted");
-        *a = pool[used++];
-        PT_HIP(hipEventRecord(*a, st));
-        ev.emplace_back(kind, *a, nullptr);
-        return PT_OK;
-    }
-    int end(hipStream_t st) {
-        if (used >= pool.size()) return pt::fail(PT_EHIP, "timing event pool exhausted");
-        hipEvent_t b = pool[used++];
-        PT_HIP(hipEventRecord(b, st));
-        std::get<2>(ev.back()) = b;
-        return PT_OK;
-    }
-    ~Timing() {
-        for (auto e : pool) (void)hipEventDestroy(e);
-    }
-};
-
-#define PT_TIMED(kind, call)                                  \
-    do {                                                      \
-        hipEvent_t a_;                                        \
-        if (tm && tm->begin(kind, st, &a_)) return PT_EHIP;   \
-        PT_HIP(call);                                         \
-        if (tm && tm->end(st)) return PT_EHIP;                \
-    } while (0)
-
-// Sample `calls` consecutive steps into the counting-sort workspace (pos / neg / destination / start,
-// calls <= csr_chunk): sampling + counting sort in LDS, one workgroup per call (then the stream advance)
-// or split over parts per call (then the destination resolve + stream advance), or the two-pass form
-// (global-atomic counts, separate scan) when no LDS plan fits. `forced` = PT_PATH_* or -1 (automatic).
-static int enqueue_sample_chunk(pt_trainer *t, pt_sampler *s, pt::CsrWork &w, int64_t bs, int64_t neg,
-                                int64_t bern, int64_t filter, int64_t calls, int forced, hipStream_t st, Timing *tm) {
-    const pt::DeviceGraph dg = s->g->dev;
-    const int64_t dpp = 1 + 2 * neg;
-    const int path = choose_path(t, calls, bs, neg, forced);
-    t->last_path = path;
-    if (w.uses) PT_HIP(hipMemsetAsync(w.uses, 0, 4 * (size_t)(w.use_stride * calls), st));   // counted by the sampler
-    w.rank_only = path == PT_PATH_PART;   // the split sampler leaves bucket ranks (the step resolves them)
-    if (path == PT_PATH_FUSED) {
-        PT_TIMED(0, pt::launch_sample_sort(dg, s->d_states, s->threads, bs, neg, (int)bern, (int)filter, calls,
-                                           t->P.ent_total, w, st));
-        PT_TIMED(1, pt::launch_advance(s->d_states, s->threads, bs, dpp * calls, st));
-    } else if (path == PT_PATH_PART) {
-        const int64_t parts = part_count(t, calls, bs);
-        pt::CsrWork wp = w;
-        if (wp.prof && calls * parts > t->prof_cap) wp.prof = nullptr;   // record only what the buffer holds
-        if (wp.prof) {
-            t->prof_calls = calls;
-            t->prof_parts = parts;
-        }
-        PT_TIMED(0, pt::launch_sample_part(dg, s->d_states, s->threads, bs, neg, (int)bern, (int)filter, calls,
-                                           parts, t->P.ent_total, wp, st));
-    } else {
-        PT_TIMED(0, pt::launch_sample_csr(dg, s->d_states, s->threads, bs, neg, (int)bern, (int)filter, calls, w, st));
-        PT_TIMED(1, pt::launch_scan_counts(w, t->P.ent_total, calls, s->d_states, s->threads, bs, dpp, st));
-    }
-    return PT_OK;
-}
-
-// Steps of a split-sampler chunk sampled ahead of the first step (0: the chunk is sampled by one launch). The
-// batch stream does not depend on the tables, so the chunk's other steps can be sampled by a second launch on
-// the trainer's side stream while the first steps train: the chunk's first step then waits for `head` steps'
-// sampling instead of the whole chunk's (the driver's 20-step chunk: 52 us). Opt-in (pt_trainer_set_sample_split;
-// the tuning build's PT_SAMPLE_SPLIT): measured slower on the driver's command, 38.4 -> 39.6 us per step at
-// head 1, 2 or 4 - the side launch's workgroups take the CUs of the steps it runs beside (step 0: 22 -> 43 us)
-// and the join across hardware queues leaves the main queue idle for ~11 us (profiles/r05_c2_split_sampling.json).
-// Not under the measurement hook (its events time each launch alone) nor for the fused step + apply.
-static int64_t sample_split_head(const pt_trainer *t, int path, int64_t calls, const Timing *tm) {
-    if (path != PT_PATH_PART || tm) return 0;
-    int64_t h = t->split_override;
-    if (h < 0) {
-        h = 0;
-        if (const char *v = pt_tuning_env("PT_SAMPLE_SPLIT")) h = atoll(v);
-    }
-    return h > 0 && h < calls ? h : 0;
-}
-
-// A split-sampler chunk in two launches: the first `head` calls on `st`, the rest on the trainer's side stream
-// forked from `st` after it (neither launch advances the streams: join_sample_split does, after both).
-static int enqueue_sample_split(pt_trainer *t, pt_sampler *s, pt::CsrWork &w, int64_t bs, int64_t neg, int64_t bern,
-                                int64_t filter, int64_t calls, int64_t head, hipStream_t st) {
-    const pt::DeviceGraph dg = s->g->dev;
-    t->last_path = PT_PATH_PART;
-    w.rank_only = 1;
-    const int64_t parts = part_count(t, calls, bs);
-    pt::CsrWork w0 = w, w1 = pt::csr_view(w, head, bs, neg);
-    w0.prof = w1.prof = nullptr;
-    w1.tick = w.tick + head;
-    PT_HIP(pt::launch_sample_part(dg, s->d_states, s->threads, bs, neg, (int)bern, (int)filter, head, parts,
-                                  t->P.ent_total, w0, st, 0, 0));
-    PT_HIP(hipEventRecord(t->ev_fork, st));
-    PT_HIP(hipStreamWaitEvent(t->side, t->ev_fork, 0));
-    PT_HIP(pt::launch_sample_part(dg, s->d_states, s->threads, bs, neg, (int)bern, (int)filter, calls - head, parts,
-                                  t->P.ent_total, w1, t->side, head, 0));
-    PT_HIP(hipEventRecord(t->ev_join, t->side));
-    return PT_OK;
-}
-// `st` waits for the side launch of enqueue_sample_split, then the streams advance past the chunk's draws
-static int join_sample_split(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, int64_t calls, hipStream_t st) {
-    PT_HIP(hipStreamWaitEvent(st, t->ev_join, 0));
-    PT_HIP(pt::launch_advance(s->d_states, s->threads, bs, (1 + 2 * neg) * calls, st));
-    return PT_OK;
-}
-
-// whether in-kernel-sampled steps of P take the fused step + apply (carved for in ensure_csr)
-static bool step_apply_on(const pt_trainer *t, const pt::StepParams &P) {
-    return step_apply_wanted(t) && t->fr.gent && t->csr.uses && pt::step_apply_supported(P, P.batch_size, P.neg);
-}
-
-// Enqueue `steps` in-kernel-sampled steps; step i adds its loss to d_losses[i]. Large neg takes the
-// counting-sort path: one sampling + one scan launch per chunk of up to kCsrChunk steps (the batch
-// stream does not depend on the tables, so it is drawn ahead), then k_step + k_apply per step.
-static int enqueue_run(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, int64_t bern, int64_t filter,
-                       int64_t steps, float *d_losses, hipStream_t st, Timing *tm = nullptr, bool assign = false) {
-    pt::StepParams P = t->P;
-    P.loss_assign = assign ? 1 : 0;   // d_losses[i] = step i's loss (no zeroing pass needed)
-    P.batch_size = bs;
-    P.neg = neg;
-    P.inv_count = 1.0f / (float)(bs * neg);
-    const int64_t dpp = 1 + 2 * neg;
-    const pt::DeviceGraph dg = s->g->dev;
-    if (use_csr(neg)) {
-        PT_CHECK(t->csr_block, PT_ESTATE, "counting-sort workspace not allocated");
-        const int64_t chunk = t->csr_chunk;
-        const bool sa = step_apply_on(t, P);
-        t->last_step_apply = sa;
-        pt::CsrWork w = t->csr;
-        if (!sa) w.uses = nullptr;   // (the sampler counts row uses only for the fused kernel)
-        for (int64_t c0 = 0; c0 < steps; c0 += chunk) {
-            const int64_t calls = std::min(chunk, steps - c0);
-            const int path = choose_path(t, calls, bs, neg, sample_mode(t));
-            const int64_t head = sa ? 0 : sample_split_head(t, path, calls, tm);
-            if (head) {
-                int rc = enqueue_sample_split(t, s, w, bs, neg, bern, filter, calls, head, st);
-                if (rc) return rc;
-            } else {
-                int rc = enqueue_sample_chunk(t, s, w, bs, neg, bern, filter, calls, sample_mode(t), st, tm);
-                if (rc) return rc;
-            }
-            t->csr.rank_only = w.rank_only;   // (read by pt_trainer_run_timed's re-timing of the last batch)
-            if (sa) {   // one launch per step, then the chunk's losses
-                // arrival words back to zero every chunk (the last arriver of a row also clears its word): a step
-                // whose arrivals ever miss a row (an aborted launch) cannot carry over past its chunk
-                PT_HIP(hipMemsetAsync(t->fr.arrive, 0, 8 * (size_t)(t->P.ent_total + t->P.rel_total), st));
-                for (int64_t j = 0; j < calls; ++j)
-                    PT_TIMED(2, pt::launch_step_apply(P, pt::csr_view(w, j, bs, neg), t->fr, st));
-                if (d_losses)
-                    PT_TIMED(3, pt::launch_loss_calls(w.lpart, bs, calls, P.inv_count, P.margin, d_losses + c0,
-                                                      P.loss_assign, st));
-                continue;
-            }
-            for (int64_t j = 0; j < calls; ++j) {
-                if (head && j == head) {   // the rest of the chunk sampled: join, then advance the streams
-                    int rc = join_sample_split(t, s, bs, neg, calls, st);
-                    if (rc) return rc;
-                }
-                const pt::CsrWork v = pt::csr_view(t->csr, j, bs, neg);
-                float *loss = d_losses ? d_losses + c0 + j : nullptr;
-                PT_TIMED(2, pt::launch_step(P, dg, s->d_states, s->threads, (int)bern, (int)filter, nullptr, nullptr,
-                                            nullptr, t->W, loss, st, &v));
-                PT_TIMED(3, pt::launch_apply(P, t->W, nullptr, 0, bs, dpp, loss, st, &v));
-            }
-        }
-    } else {
-        t->last_path = PT_PATH_SAMPLED;
-        t->last_step_apply = false;
-        for (int64_t i = 0; i < steps; ++i) {
-            float *loss = d_losses ? d_losses + i : nullptr;
-            PT_TIMED(2, pt::launch_step(P, dg, s->d_states, s->threads, (int)bern, (int)filter, nullptr, nullptr,
-                                        nullptr, t->W, loss, st));
-            PT_TIMED(3, pt::launch_apply(P, t->W, s->d_states, s->threads, bs, dpp, loss, st));
-        }
-    }
-    return PT_OK;
-}
-
-static int enqueue_external(pt_trainer *t, int64_t bs, int64_t neg, const int64_t *bh, const int64_t *bt,
-                            const int64_t *br, float *d_loss, hipStream_t st) {
-    pt::StepParams P = t->P;
-    P.batch_size = bs;
-    P.neg = neg;
-    P.inv_count = 1.0f / (float)(bs * neg);
-    PT_HIP(pt::launch_step(P, pt::DeviceGraph{}, nullptr, 0, 0, 0, bh, bt, br, t->W, d_loss, st));
-    PT_HIP(pt::launch_apply(P, t->W, nullptr, 0, bs, 1 + 2 * neg, d_loss, st));
-    return PT_OK;
-}
-
-// per-positive loss partials for batches of up to `bs` positives (grown on demand, never during a
-// capture: callers prepare before enqueueing)
-static int ensure_lpart(pt_trainer *t, int64_t bs) {
-    if (bs <= t->lpart_cap) return PT_OK;
-    PT_HIP(hipDeviceSynchronize());   // queued work may still use the old buffer
-    t->drop_graphs();
-    if (t->W.lpart) (void)hipFree(t->W.lpart);
-    t->W.lpart = nullptr;
-    t->lpart_cap = 0;
-    PT_HIP(hipMalloc(&t->W.lpart, sizeof(float) * (size_t)bs));
-    t->lpart_cap = bs;
-    return PT_OK;
-}
-
-static int prepare_sampled(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, int64_t steps) {
-    int rc = check_step_args(t->P, s, bs, neg, nullptr);
-    if (rc) return rc;
-    rc = ensure_lpart(t, bs);
-    if (rc) return rc;
-    rc = s->g->upload();
-    if (rc) return rc;
-    (void)steps;
-    if (use_csr(neg)) return ensure_csr(t, bs, neg);
-    return PT_OK;
-}
-
-// ---- reference-order mode (ordered.hip): workspace for batches of up to `seq` slots
-static int ensure_ordered(pt_trainer *t, int64_t seq) {
-    const int64_t D = t->P.dim;
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t need = 3 * al(8 * seq) + 3 * al(4 * seq) + al(16 * (size_t)seq * D);
-    if (need <= t->ord_cap) return PT_OK;
-    PT_HIP(hipDeviceSynchronize());   // queued ordered steps may still use the old block
-    if (t->ord_block) (void)hipFree(t->ord_block);
-    t->ord_block = nullptr;
-    t->ord_cap = 0;
-    PT_HIP(hipMalloc(&t->ord_block, need));
-    t->ord_cap = need;
-    char *b = (char *)t->ord_block;
-    t->ord_h = (int64_t *)b; b += al(8 * seq);
-    t->ord_t = (int64_t *)b; b += al(8 * seq);
-    t->ord_r = (int64_t *)b; b += al(8 * seq);
-    t->ord_y = (float *)b; b += al(4 * seq);
-    t->ord_score = (float *)b; b += al(4 * seq);
-    t->ord_ds = (float *)b; b += al(4 * seq);
-    t->ord_g = (float *)b;
-    return PT_OK;
-}
-
-static int enqueue_ordered(pt_trainer *t, int64_t bs, int64_t neg, const int64_t *bh, const int64_t *bt,
-                           const int64_t *br, float *loss, int assign, hipStream_t st) {
-    const pt::StepParams &P = t->P;
-    pt::OrderedStep S{};
-    S.model = P.model; S.p_norm = P.p_norm; S.norm_flag = P.norm_flag; S.opt = P.opt;
-    S.lr = P.lr; S.margin = P.margin;
-    S.ent_total = P.ent_total; S.rel_total = P.rel_total; S.dim = P.dim;
-    S.ent = P.ent; S.rel = P.rel; S.normv = P.normv;
-    S.ent_acc = P.ent_acc; S.rel_acc = P.rel_acc; S.norm_acc = P.norm_acc;
-    S.h = bh; S.t = bt; S.r = br;
-    S.bs = bs; S.neg = neg; S.seq = bs * (1 + neg);
-    S.score = t->ord_score; S.ds = t->ord_ds;
-    S.gh = t->ord_g; S.gt = S.gh + S.seq * P.dim; S.gr = S.gt + S.seq * P.dim; S.gw = S.gr + S.seq * P.dim;
-    PT_HIP(pt::launch_ordered_step(S, loss, assign, st));
-    return PT_OK;
-}
-
-// `steps` sampled steps in reference order: k_sample's batch (bit-identical to sampling()), then the step
-static int enqueue_ordered_run(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, int64_t bern, int64_t filter,
-                               int64_t steps, float *d_losses, int assign, hipStream_t st) {
-    PT_CHECK(s && s->g && s->d_states, PT_ESTATE, "in-kernel sampling needs a sampler bound to a graph");
-    PT_CHECK(s->g->ent_total > 1, PT_EINVAL, "graph needs at least two entities");
-    PT_CHECK(s->g->ent_total <= t->P.ent_total && s->g->rel_total <= t->P.rel_total, PT_EINVAL,
-             "graph ids exceed the model tables");
-    int rc = s->g->upload();
-    if (rc) return rc;
-    rc = ensure_ordered(t, bs * (1 + neg));
-    if (rc) return rc;
-    t->last_path = -1;
-    for (int64_t i = 0; i < steps; ++i) {
-        PT_HIP(pt::launch_sample(s->g->dev, s->d_states, s->threads, bs, neg, 0, 0, (int)bern, (int)filter, t->ord_h,
-                                 t->ord_t, t->ord_r, t->ord_y, st));
-        PT_HIP(pt::launch_advance(s->d_states, s->threads, bs, 1 + 2 * neg, st));
-        rc = enqueue_ordered(t, bs, neg, t->ord_h, t->ord_t, t->ord_r, d_losses ? d_losses + i : nullptr, assign, st);
-        if (rc) return rc;
-    }
-    return PT_OK;
-}
-
-extern "C" int pt_trainer_set_sampling(pt_trainer *t, int32_t path, int64_t parts) {
-    PT_CHECK(t, PT_EINVAL, "null trainer");
-    PT_CHECK(path >= -1 && path <= PT_PATH_PART, PT_EINVAL, "sampling path must be -1 or PT_PATH_FUSED/PART/TWO_PASS");
-    PT_CHECK(parts >= 0, PT_EINVAL, "parts must be >= 0");
-    t->path_override = path;
-    t->parts_override = parts;
-    t->drop_graphs();   // captured epochs hold the previous choice
-    return PT_OK;
-}
-
-extern "C" int pt_trainer_set_sample_split(pt_trainer *t, int64_t head) {
-    PT_CHECK(t, PT_EINVAL, "null trainer");
-    PT_CHECK(head >= -1, PT_EINVAL, "head must be >= -1");
-    t->split_override = head;
-    t->drop_graphs();   // captured epochs hold the previous choice
-    return PT_OK;
-}
-
-extern "C" int pt_trainer_set_deterministic(pt_trainer *t, int32_t on) {
-    PT_CHECK(t, PT_EINVAL, "null trainer");
-    PT_CHECK(!on || pt::ordered_dim_supported(t->P.dim), PT_ENOTSUP, "reference-order mode: dim too large");
-    t->ordered = on != 0;
-    return PT_OK;
-}
-extern "C" int pt_trainer_get_deterministic(const pt_trainer *t) { return t && t->ordered ? 1 : 0; }
-
-extern "C" int pt_trainer_step(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, int64_t bern, int64_t filter,
-                               const int64_t *d_bh, const int64_t *d_bt, const int64_t *d_br, float *d_loss,
-                               void *stream) {
-    PT_CHECK(t, PT_EINVAL, "null trainer");
-    if (d_bh) {
-        PT_CHECK(d_bt && d_br, PT_EINVAL, "external batch needs h, t and r arrays");
-        PT_CHECK(bs > 0 && neg > 0, PT_EINVAL, "batch_size and neg_ent must be positive");
-        if (t->ordered) {
-            int rc = ensure_ordered(t, bs * (1 + neg));
-            if (rc) return rc;
-            return enqueue_ordered(t, bs, neg, d_bh, d_bt, d_br, d_loss, 0, (hipStream_t)stream);
-        }
-        int rc = ensure_lpart(t, bs);
-        if (rc) return rc;
-        return enqueue_external(t, bs, neg, d_bh, d_bt, d_br, d_loss, (hipStream_t)stream);
-    }
-    PT_CHECK(bs > 0 && neg > 0, PT_EINVAL, "batch_size and neg_ent must be positive");
-    if (t->ordered) return enqueue_ordered_run(t, s, bs, neg, bern, filter, 1, d_loss, 0, (hipStream_t)stream);
-    int rc = prepare_sampled(t, s, bs, neg, 1);
-    if (rc) return rc;
-    return enqueue_run(t, s, bs, neg, bern, filter, 1, d_loss, (hipStream_t)stream);
-}
-
-// `steps` in-kernel-sampled steps launched one by one with an event pair around every launch on
-// `stream` (measurement hook for bench.py's roofline). ms4[k] = total duration of kernel kind k
-// (0 sampling, 1 bucket scan, 2 forward/backward, 3 optimizer) divided by `steps`. Synchronizes.
-extern "C" int pt_trainer_run_timed(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, int64_t bern,
-                                    int64_t filter, int64_t steps, float *d_losses, float *ms4, void *stream) {
-    PT_CHECK(t && ms4 && steps > 0, PT_EINVAL, "pt_trainer_run_timed: bad argument");
-    PT_CHECK(!t->ordered, PT_ENOTSUP, "pt_trainer_run_timed times the fast path (reference-order mode is on)");
-    int rc = prepare_sampled(t, s, bs, neg, steps);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    Timing tm;
-    rc = tm.reserve((size_t)(8 * steps + 64));
-    if (rc) return rc;
-    // hold the stream in a short spin kernel while the host enqueues every measured launch, so each
-    // kernel starts as soon as its predecessor ends (no host-side gaps inside an event pair)
-    PT_HIP(pt::launch_spin(20000, st));
-    rc = enqueue_run(t, s, bs, neg, bern, filter, steps, d_losses, st, &tm, true);
-    if (rc) return rc;
-    PT_HIP(hipStreamSynchronize(st));
-    double tot[4] = {0, 0, 0, 0};
-    for (auto &e : tm.ev) {
-        float ms = 0;
-        PT_HIP(hipEventElapsedTime(&ms, std::get<1>(e), std::get<2>(e)));
-        tot[std::get<0>(e)] += ms;
-    }
-    for (int k = 0; k < 4; ++k) ms4[k] = (float)(tot[k] / (double)steps);
-    if (t->csr.prof && t->last_path == PT_PATH_PART && t->prof_calls > 0) {   // split sampler phases of the last chunk
-        const int64_t calls = t->prof_calls, parts = t->prof_parts;
-        std::vector<uint64_t> pr((size_t)(8 * calls * parts));
-        PT_HIP(hipMemcpy(pr.data(), t->csr.prof, 8 * pr.size(), hipMemcpyDeviceToHost));
-        uint64_t t0 = ~0ull, tend = 0;
-        double ph[7] = {0}, mx[7] = {0};
-        int64_t n_last = 0;
-        double last5 = 0, last6 = 0;
-        for (int64_t i = 0; i < calls * parts; ++i) t0 = std::min(t0, pr[8 * i]);
-        for (int64_t i = 0; i < calls * parts; ++i) {
-            const uint64_t *q = &pr[8 * i];
-            for (int k = 1; k <= 4; ++k) {
-                ph[k] += (double)(q[k] - q[k - 1]);
-                mx[k] = std::max(mx[k], (double)(q[k] - t0));
-            }
-            mx[0] = std::max(mx[0], (double)(q[0] - t0));
-            if (q[7]) {
-                ++n_last;
-                last5 += (double)(q[5] - q[4]);
-                last6 += (double)(q[6] - q[5]);
-                tend = std::max(tend, q[6]);
-            }
-        }
-        const double n = (double)(calls * parts);
-        fprintf(stderr,
-                "part-prof calls %ld parts %ld: avg us positives %.2f slots %.2f reserve %.2f rank+ticket %.2f | "
-                "last exchange %.2f scan %.2f | latest start %.2f, phase ends (max from first start) %.2f %.2f %.2f "
-                "%.2f, kernel end %.2f\n",
-                (long)calls, (long)parts, ph[1] / n / 100, ph[2] / n / 100, ph[3] / n / 100, ph[4] / n / 100,
-                last5 / std::max<int64_t>(n_last, 1) / 100, last6 / std::max<int64_t>(n_last, 1) / 100, mx[0] / 100,
-                mx[1] / 100, mx[2] / 100, mx[3] / 100, mx[4] / 100, (double)(tend - t0) / 100);
-    }
-    if (!use_csr(neg)) return PT_OK;
-    // Counting-sort path: the per-step kernels are re-timed back to back (as a captured epoch runs
-    // them), one event pair per loop instead of one per launch, on the last pre-sampled batch:
-    //   loop 1: `steps` x (forward/backward, apply)  -> T_sa;   loop 2: `steps` x forward/backward -> T_s
-    // ms4[2] = T_s / steps, ms4[3] = (T_sa - T_s) / steps. The tables, Adagrad state, gradient rows and
-    // flags are restored afterwards, so training state is exactly as the measured run left it.
-    pt::StepParams P = t->P;
-    P.batch_size = bs;
-    P.neg = neg;
-    P.inv_count = 1.0f / (float)(bs * neg);
-    const int64_t E = P.ent_total, R = P.rel_total, D = P.dim, dpp = 1 + 2 * neg;
-    std::vector<std::pair<float *, size_t>> keep = {{P.ent, 4 * E * D}, {P.rel, 4 * R * D}};
-    if (P.normv) keep.push_back({P.normv, 4 * R * D});
-    if (P.opt != 0) {
-        keep.push_back({P.ent_acc, 4 * E * D});
-        keep.push_back({P.rel_acc, 4 * R * D});
-        if (P.norm_acc) keep.push_back({P.norm_acc, 4 * R * D});
-    }
-    size_t nb = 0;
-    for (auto &k : keep) nb += k.second;
-    char *bak = nullptr;
-    PT_HIP(hipMalloc(&bak, nb));
-    size_t off = 0;
-    for (auto &k : keep) {
-        PT_HIP(hipMemcpyAsync(bak + off, k.first, k.second, hipMemcpyDeviceToDevice, st));
-        off += k.second;
-    }
-    const pt::DeviceGraph dg = s->g->dev;
-    const pt::CsrWork v = pt::csr_view(t->csr, 0, bs, neg);
-    hipEvent_t ev[4] = {tm.pool[0], tm.pool[1], tm.pool[2], tm.pool[3]};
-    int erc = PT_OK;
-    if (pt::launch_spin(20000, st) != hipSuccess || hipEventRecord(ev[0], st) != hipSuccess) erc = PT_EHIP;
-    // the fused step + apply: loop 1 only (ms4[3] keeps the chunks' loss kernels from the pass above)
-    const bool sa = t->last_step_apply;
-    for (int64_t i = 0; i < steps && !erc; ++i) {
-        if (sa) {
-            if (pt::launch_step_apply(P, v, t->fr, st) != hipSuccess) erc = PT_EHIP;
-            continue;
-        }
-        if (pt::launch_step(P, dg, s->d_states, s->threads, (int)bern, (int)filter, nullptr, nullptr, nullptr, t->W,
-                            nullptr, st, &v) != hipSuccess ||
-            pt::launch_apply(P, t->W, nullptr, 0, bs, dpp, nullptr, st, &v) != hipSuccess)
-            erc = PT_EHIP;
-    }
-    if (!erc && (hipEventRecord(ev[1], st) != hipSuccess || pt::launch_spin(20000, st) != hipSuccess ||
-                 hipEventRecord(ev[2], st) != hipSuccess))
-        erc = PT_EHIP;
-    for (int64_t i = 0; i < steps && !erc && !sa; ++i) {
-        if (pt::launch_step(P, dg, s->d_states, s->threads, (int)bern, (int)filter, nullptr, nullptr, nullptr, t->W,
-                            nullptr, st, &v) != hipSuccess)
-            erc = PT_EHIP;
-    }
-    if (!erc && hipEventRecord(ev[3], st) != hipSuccess) erc = PT_EHIP;
-    // restore
-    off = 0;
-    for (auto &k : keep) {
-        if (hipMemcpyAsync(k.first, bak + off, k.second, hipMemcpyDeviceToDevice, st) != hipSuccess) erc = PT_EHIP;
-        off += k.second;
-    }
-    if (hipMemsetAsync(t->ws_block, 0, t->ws_bytes, st) != hipSuccess) erc = PT_EHIP;
-    const hipError_t se = hipStreamSynchronize(st);
-    (void)hipFree(bak);
-    if (erc) return pt::fail(erc, "pt_trainer_run_timed: isolation timing launch failed");
-    PT_HIP(se);
-    float t_sa = 0, t_s = 0;
-    PT_HIP(hipEventElapsedTime(&t_sa, ev[0], ev[1]));
-    PT_HIP(hipEventElapsedTime(&t_s, ev[2], ev[3]));
-    if (sa) {
-        ms4[2] = t_sa / (float)steps;
-    } else {
-        ms4[2] = t_s / (float)steps;
-        ms4[3] = (t_sa - t_s) / (float)steps;
-    }
-    return PT_OK;
-}
-
-extern "C" int pt_trainer_set_step_apply(pt_trainer *t, int32_t on) {
-    PT_CHECK(t, PT_EINVAL, "null trainer");
-    if (t->step_apply_on != (on != 0)) t->csr_bs = 0;   // re-carve the workspace: the fused kernel's state only when on
-    t->step_apply_on = on != 0;
-    t->drop_graphs();   // captured epochs hold the previous choice
-    return PT_OK;
-}
-extern "C" int pt_trainer_step_apply(const pt_trainer *t) { return t && t->last_step_apply ? 1 : 0; }
-
-extern "C" int pt_trainer_set_slot_scale(pt_trainer *t, int32_t on) {
-    PT_CHECK(t, PT_EINVAL, "null trainer");
-    if (t->slot_scale_on != (on != 0)) t->csr_bs = 0;   // re-carve the workspace (slot records / base rows)
-    t->slot_scale_on = on != 0;
-    t->drop_graphs();
-    return PT_OK;
-}
-extern "C" int pt_trainer_slot_scale(const pt_trainer *t) { return t && t->csr.slot_scale ? 1 : 0; }
-
-extern "C" int pt_trainer_last_path(const pt_trainer *t) { return t ? t->last_path : -1; }
-
-extern "C" int pt_trainer_sample_csr(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, int64_t bern,
-                                     int64_t filter, int64_t calls, int32_t path, int32_t *h_pos, int32_t *h_neg,
-                                     int32_t *h_dst, int32_t *h_start, void *stream) {
-    PT_CHECK(t && s && h_pos && h_neg && h_dst && h_start, PT_EINVAL, "pt_trainer_sample_csr: null argument");
-    PT_CHECK(calls > 0, PT_EINVAL, "pt_trainer_sample_csr: calls must be positive");
-    PT_CHECK(path >= -1 && path <= PT_PATH_PART, PT_EINVAL, "pt_trainer_sample_csr: path must be -1 or PT_PATH_*");
-    int rc = prepare_sampled(t, s, bs, neg, calls);
-    if (rc) return rc;
-    if (!t->csr_block) {   // small neg runs the in-step sampler; carve the counting-sort workspace anyway
-        rc = ensure_csr(t, bs, neg);
-        if (rc) return rc;
-    }
-    PT_CHECK(calls <= t->csr_chunk, PT_EINVAL, "pt_trainer_sample_csr: calls exceeds the workspace chunk");
-    if (path == PT_PATH_FUSED) PT_CHECK(t->csr_fused, PT_ENOTSUP, "fused sampling plan does not fit LDS");
-    if (path == PT_PATH_PART)
-        PT_CHECK(t->csr_part && pt::sample_part_fits(bs, neg, t->P.ent_total, part_count(t, calls, bs)), PT_ENOTSUP,
-                 "split sampling plan does not fit LDS");
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t head = path == PT_PATH_PART && t->split_override > 0 && t->split_override < calls ? t->split_override
-                                                                                                    : 0;
-    if (head) {   // the split pair (pt_trainer_set_sample_split), joined before the copies
-        rc = enqueue_sample_split(t, s, t->csr, bs, neg, bern, filter, calls, head, st);
-        if (!rc) rc = join_sample_split(t, s, bs, neg, calls, st);
-    } else {
-        rc = enqueue_sample_chunk(t, s, t->csr, bs, neg, bern, filter, calls, path, st, nullptr);
-    }
-    if (rc) return rc;
-    const pt::CsrWork &w = t->csr;
-    const int64_t E = t->P.ent_total, slots = bs * neg;
-    std::vector<int4> pos((size_t)(calls * bs));
-    PT_HIP(hipMemcpyAsync(pos.data(), w.pos, sizeof(int4) * pos.size(), hipMemcpyDeviceToHost, st));
-    PT_HIP(hipMemcpyAsync(h_neg, w.neg, 4 * (size_t)(calls * slots), hipMemcpyDeviceToHost, st));
-    PT_HIP(hipMemcpyAsync(h_dst, w.off, 4 * (size_t)(calls * slots), hipMemcpyDeviceToHost, st));
-    PT_HIP(hipMemcpy2DAsync(h_start, 4 * (size_t)(E + 1), w.start, 4 * (size_t)w.start_stride, 4 * (size_t)(E + 1),
-                            (size_t)calls, hipMemcpyDeviceToHost, st));
-    PT_HIP(hipStreamSynchronize(st));
-    if (w.rank_only)   // split sampler: ranks inside the buckets -> destination rows
-        for (int64_t c = 0; c < calls; ++c)
-            for (int64_t o = 0; o < slots; ++o)
-                h_dst[c * slots + o] += h_start[c * (E + 1) + (h_neg[c * slots + o] >> 1)];
-    for (size_t i = 0; i < pos.size(); ++i) {
-        h_pos[3 * i] = pos[i].x;
-        h_pos[3 * i + 1] = pos[i].y;
-        h_pos[3 * i + 2] = pos[i].z;
-    }
-    return PT_OK;
-}
-
-extern "C" int pt_trainer_run(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, int64_t bern, int64_t filter,
-                              int64_t steps, float *d_losses, void *stream) {
-    PT_CHECK(t && d_losses, PT_EINVAL, "pt_trainer_run: null argument");
-    PT_CHECK(steps > 0, PT_EINVAL, "steps must be positive");
-    if (t->ordered) {
-        PT_CHECK(bs > 0 && neg > 0, PT_EINVAL, "batch_size and neg_ent must be positive");
-        return enqueue_ordered_run(t, s, bs, neg, bern, filter, steps, d_losses, 1, (hipStream_t)stream);
-    }
-    int rc = prepare_sampled(t, s, bs, neg, steps);
-    if (rc) return rc;
-    GraphKey key{s, s->g->dev.rec, d_losses, s->d_states, bs, neg, bern, filter, steps};
-    auto it = t->graphs.find(key);
-    if (it == t->graphs.end()) {
-        hipGraph_t graph;
-        PT_HIP(hipStreamBeginCapture(t->cap, hipStreamCaptureModeThreadLocal));
-        int erc = PT_OK;
-        erc = enqueue_run(t, s, bs, neg, bern, filter, steps, d_losses, t->cap, nullptr, true);
-        hipError_t ce = hipStreamEndCapture(t->cap, &graph);
-        if (erc) return erc;
-        PT_HIP(ce);
-        hipGraphExec_t exec;
-        hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        PT_HIP(ie);
-        it = t->graphs.emplace(key, exec).first;
-    }
-    PT_HIP(hipGraphLaunch(it->second, (hipStream_t)stream));
-    return PT_OK;
-}
-
+// ======================================================================== scoring and metrics ====
 extern "C" int pt_score(const pt_model_desc *m, int32_t mode, const int64_t *d_h, const int64_t *d_t,
                         const int64_t *d_r, int64_t n, float *d_out, void *stream) {
     pt::StepParams P{};
     pt_model_desc mm = *m;
     if (!mm.ent_acc) { mm.opt = PT_SGD; }
-    int rc = desc_to_params(&mm, P);
+    int rc = pt::desc_to_params(&mm, P);
     if (rc) return rc;
     PT_CHECK(mode >= 0 && mode <= 2, PT_EINVAL, "mode must be 0 (normal), 1 (head_batch) or 2 (tail_batch)");
     PT_CHECK(d_h && d_t && d_r && d_out, PT_EINVAL, "pt_score: null argument");
@@ -1038,7 +184,7 @@ extern "C" int pt_score_queries(const pt_model_desc *m, int32_t side, const int6
     pt::StepParams P{};
     pt_model_desc mm = *m;
     if (!mm.ent_acc) mm.opt = PT_SGD;
-    int rc = desc_to_params(&mm, P);
+    int rc = pt::desc_to_params(&mm, P);
     if (rc) return rc;
     PT_CHECK(side == 0 || side == 1, PT_EINVAL, "side must be 0 (head prediction) or 1 (tail prediction)");
     PT_CHECK(nq <= 65535, PT_EINVAL, "at most 65535 queries per call");
@@ -1052,7 +198,7 @@ extern "C" int pt_score_rows(const pt_model_desc *m, int32_t side, const int64_t
     pt::StepParams P{};
     pt_model_desc mm = *m;
     if (!mm.ent_acc) mm.opt = PT_SGD;
-    int rc = desc_to_params(&mm, P);
+    int rc = pt::desc_to_params(&mm, P);
     if (rc) return rc;
     PT_CHECK(side == 0 || side == 1, PT_EINVAL, "side must be 0 (head prediction) or 1 (tail prediction)");
     PT_CHECK(nq <= 65535, PT_EINVAL, "at most 65535 queries per call");
@@ -1388,7 +534,7 @@ void legacy_err(int rc) {
 
 int legacy_sync_sampler(Legacy &l) {
     if (!l.sampler_ready) {
-        int rc = sampler_init(&l.sampler, nullptr, 64, nullptr);
+        int rc = pt::sampler_init(&l.sampler, nullptr, 64, nullptr);
         if (rc) return rc;
         l.sampler.threads = std::max<int64_t>(1, l.threads);
         l.sampler_ready = true;

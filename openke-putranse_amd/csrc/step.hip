@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void k_step(StepParams P, const int64_t *__res
 //
 // CSR = true: the batch was drawn by k_sample_csr; the corrupted entities' gradient rows are written
 // with plain stores to their counting-sort slots (contrib) instead of float atomics.
-template <int MODEL, int G, int VEC, int KCH, int NCH, int S, bool CSR, bool DB>
+template <int MODEL, int G, int VEC, int KCH, int NCH, int S, bool CSR>
 __global__ __launch_bounds__(256) void k_step_sampled(StepParams P, DeviceGraph g, const uint64_t *__restrict__ states,
                                                       int64_t threads, int bern, int filter, GlobalSink sink,
                                                       float *__restrict__ loss, CsrWork cw) {
@@ -143,8 +143,7 @@ __global__ __launch_bounds__(256) void k_step_sampled(StepParams P, DeviceGraph 
     const bool nf = P.norm_flag != 0;
     const int64_t hp = pd.h, rp = pd.r, tp = pd.t;
     const int64_t *mine = s_neg + pl * neg;
-    // DB: double buffer (the next chunk's rows load while this chunk computes), for nper > NCH
-    Vec EA[NCH], EB[DB ? NCH : 1];
+    Vec EA[NCH];
     Vec aH, aT, aR, aW;
     vzero(aH); vzero(aT); vzero(aR); vzero(aW);
     float csum = 0.f, lsum = 0.f;
@@ -240,23 +239,11 @@ __global__ __launch_bounds__(256) void k_step_sampled(StepParams P, DeviceGraph 
                 }
             }
         };
-        if constexpr (DB) {
-            for (int64_t c0 = k_lo; c0 < k_hi;) {
-                if (c0 + NCH < k_hi) load_chunk(EB, c0 + NCH);
-                process(EA, c0);
-                c0 += NCH;
-                if (c0 >= k_hi) break;
-                if (c0 + NCH < k_hi) load_chunk(EA, c0 + NCH);
-                process(EB, c0);
-                c0 += NCH;
-            }
-        } else {
-            for (int64_t c0 = k_lo; c0 < k_hi;) {
-                process(EA, c0);
-                c0 += NCH;
-                if (c0 >= k_hi) break;
-                load_chunk(EA, c0);
-            }
+        for (int64_t c0 = k_lo; c0 < k_hi;) {
+            process(EA, c0);
+            c0 += NCH;
+            if (c0 >= k_hi) break;
+            load_chunk(EA, c0);
         }
     }
     if constexpr (S > 1) {
@@ -599,17 +586,17 @@ int pick_nch(int64_t neg, int kch) {
 
 // VEC=1 shapes x NCH x S of the sampled step kernel: S = 1 for neg < 8 (NCH covers neg), S = 4 with
 // NCH covering ceil(neg/4) (chunks beyond 32 negatives per sub-group loop)
-#define PT_SSHAPES(X)                                                                                  \
-    X(2, 1, 1, 1, 1, false) X(2, 1, 1, 4, 1, false) X(2, 1, 1, 8, 1, false) X(2, 1, 1, 8, 4, false) X(2, 1, 1, 32, 4, false)                  \
-    X(4, 1, 1, 1, 1, false) X(4, 1, 1, 4, 1, false) X(4, 1, 1, 8, 1, false) X(4, 1, 1, 8, 4, false) X(4, 1, 1, 32, 4, false)                  \
-    X(8, 1, 1, 1, 1, false) X(8, 1, 1, 4, 1, false) X(8, 1, 1, 8, 1, false) X(8, 1, 1, 8, 4, false) X(8, 1, 1, 32, 4, false)                  \
-    X(16, 1, 1, 1, 1, false) X(16, 1, 1, 4, 1, false) X(16, 1, 1, 8, 1, false) X(16, 1, 1, 8, 4, false) X(16, 1, 1, 32, 4, false)             \
-    X(32, 1, 1, 1, 1, false) X(32, 1, 1, 4, 1, false) X(32, 1, 1, 8, 1, false) X(32, 1, 1, 8, 4, false) X(32, 1, 1, 32, 4, false)             \
-    X(64, 1, 1, 1, 1, false) X(64, 1, 1, 4, 1, false) X(64, 1, 1, 8, 1, false) X(64, 1, 1, 8, 4, false) X(64, 1, 1, 32, 4, false)             \
-    X(64, 1, 2, 1, 1, false) X(64, 1, 2, 4, 1, false) X(64, 1, 2, 8, 1, false) X(64, 1, 2, 8, 4, false) X(64, 1, 2, 32, 4, false)             \
-    X(64, 1, 4, 1, 1, false) X(64, 1, 4, 4, 1, false) X(64, 1, 4, 8, 1, false) X(64, 1, 4, 8, 4, false) X(64, 1, 4, 32, 4, false)             \
-    X(64, 1, 4, 8, 2, false) X(64, 1, 4, 4, 4, false) X(64, 1, 4, 4, 2, false)                             \
-    X(64, 1, 8, 1, 1, false) X(64, 1, 8, 4, 1, false) X(64, 1, 8, 8, 1, false) X(64, 1, 8, 8, 4, false)
+#define PT_SSHAPES(X)                                                                                 \
+    X(2, 1, 1, 1, 1) X(2, 1, 1, 4, 1) X(2, 1, 1, 8, 1) X(2, 1, 1, 8, 4) X(2, 1, 1, 32, 4)             \
+    X(4, 1, 1, 1, 1) X(4, 1, 1, 4, 1) X(4, 1, 1, 8, 1) X(4, 1, 1, 8, 4) X(4, 1, 1, 32, 4)             \
+    X(8, 1, 1, 1, 1) X(8, 1, 1, 4, 1) X(8, 1, 1, 8, 1) X(8, 1, 1, 8, 4) X(8, 1, 1, 32, 4)             \
+    X(16, 1, 1, 1, 1) X(16, 1, 1, 4, 1) X(16, 1, 1, 8, 1) X(16, 1, 1, 8, 4) X(16, 1, 1, 32, 4)        \
+    X(32, 1, 1, 1, 1) X(32, 1, 1, 4, 1) X(32, 1, 1, 8, 1) X(32, 1, 1, 8, 4) X(32, 1, 1, 32, 4)        \
+    X(64, 1, 1, 1, 1) X(64, 1, 1, 4, 1) X(64, 1, 1, 8, 1) X(64, 1, 1, 8, 4) X(64, 1, 1, 32, 4)        \
+    X(64, 1, 2, 1, 1) X(64, 1, 2, 4, 1) X(64, 1, 2, 8, 1) X(64, 1, 2, 8, 4) X(64, 1, 2, 32, 4)        \
+    X(64, 1, 4, 1, 1) X(64, 1, 4, 4, 1) X(64, 1, 4, 8, 1) X(64, 1, 4, 8, 4) X(64, 1, 4, 32, 4)        \
+    X(64, 1, 4, 8, 2) X(64, 1, 4, 4, 4) X(64, 1, 4, 4, 2)                                             \
+    X(64, 1, 8, 1, 1) X(64, 1, 8, 4, 1) X(64, 1, 8, 8, 1) X(64, 1, 8, 8, 4)
 
 }  // namespace
 // k_step_csr instances (G, KCH, NCH), float4 lanes
@@ -712,40 +699,35 @@ hipError_t launch_step(const StepParams &P, const DeviceGraph &g, const uint64_t
         const int64_t nper = (P.neg + S - 1) / S;
         int nch = pick_nch(nper, s.KCH * s.VEC);
         if (const char *v = pt_tuning_env("PT_STEP_NCH")) nch = atoi(v);
-        // double-buffer the negative rows when a lane group takes more than one chunk (PT_STEP_DB=0 off)
-        bool db = nper > nch;
-        if (const char *v = pt_tuning_env("PT_STEP_DB")) db = db && atoi(v) != 0;
         const int64_t gpb = 256 / s.G, ppb = gpb / S;
         const dim3 grid((unsigned)((P.batch_size + ppb - 1) / ppb)), block(256);
         size_t lds = (size_t)ppb * (size_t)P.neg * sizeof(int64_t) * (csr ? 2 : 1);
         if (S > 1) lds += sizeof(float) * ((size_t)gpb * 4 * s.KCH * s.G * s.VEC + (size_t)gpb * 2);
         if (lds > 64 * 1024) return hipErrorInvalidValue;
         const CsrWork cw = csr ? *csr : CsrWork{};
-#define PT_SSTEP(G_, V_, K_, N_, S_, DB_)                                                                            \
-        if (s.G == G_ && s.VEC == V_ && s.KCH == K_ && nch == N_ && S == S_ && db == DB_) {                              \
+#define PT_SSTEP(G_, V_, K_, N_, S_)                                                                                 \
+        if (s.G == G_ && s.VEC == V_ && s.KCH == K_ && nch == N_ && S == S_) {                                           \
             if (csr) {                                                                                            \
                 if (P.model == 0)                                                                                 \
-                    hipLaunchKernelGGL((dev::k_step_sampled<0, G_, V_, K_, N_, S_, true, DB_>), grid, block, lds, st,   \
+                    hipLaunchKernelGGL((dev::k_step_sampled<0, G_, V_, K_, N_, S_, true>), grid, block, lds, st,        \
                                        P, g, states, threads, bern, filter, sink, loss, cw);                      \
                 else                                                                                              \
-                    hipLaunchKernelGGL((dev::k_step_sampled<1, G_, V_, K_, N_, S_, true, DB_>), grid, block, lds, st,   \
+                    hipLaunchKernelGGL((dev::k_step_sampled<1, G_, V_, K_, N_, S_, true>), grid, block, lds, st,        \
                                        P, g, states, threads, bern, filter, sink, loss, cw);                      \
             } else {                                                                                              \
                 if (P.model == 0)                                                                                 \
-                    hipLaunchKernelGGL((dev::k_step_sampled<0, G_, V_, K_, N_, S_, false, DB_>), grid, block, lds, st,  \
+                    hipLaunchKernelGGL((dev::k_step_sampled<0, G_, V_, K_, N_, S_, false>), grid, block, lds, st,       \
                                        P, g, states, threads, bern, filter, sink, loss, cw);                      \
                 else                                                                                              \
-                    hipLaunchKernelGGL((dev::k_step_sampled<1, G_, V_, K_, N_, S_, false, DB_>), grid, block, lds, st,  \
+                    hipLaunchKernelGGL((dev::k_step_sampled<1, G_, V_, K_, N_, S_, false>), grid, block, lds, st,       \
                                        P, g, states, threads, bern, filter, sink, loss, cw);                      \
             }                                                                                                     \
             return hipGetLastError();                                                                             \
         }
-        // the preferred chunk size first, then any instantiated one (the kernel loops over chunks);
-        // double-buffered instances are tuning experiments only
-        const int cands[6] = {nch, nch, 8, 4, 32, 1};
-        for (int ci = 0; ci < 6; ++ci) {
+        // the preferred chunk size first, then any instantiated one (the kernel loops over chunks)
+        const int cands[5] = {nch, 8, 4, 32, 1};
+        for (int ci = 0; ci < 5; ++ci) {
             nch = cands[ci];
-            if (ci > 0) db = false;
             PT_SSHAPES(PT_SSTEP)
         }
 #undef PT_SSTEP

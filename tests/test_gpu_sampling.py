@@ -2,7 +2,7 @@
 
 The large-neg training step (C2) reads its batch in a counting-sort layout: positives, one record per
 (positive, negative) slot, and every slot's destination row inside its corrupted entity's bucket. Three
-kernels produce it (capi.cpp enqueue_sample_chunk):
+kernels produce it (trainer.cpp enqueue_sample_chunk):
   * PT_PATH_FUSED    k_sample_sort: one workgroup per call, everything in LDS;
   * PT_PATH_PART     k_sample_part + k_resolve: `parts` workgroups per call, global bucket reservation,
                      the last part scans;
@@ -198,3 +198,19 @@ def test_split_sampling_run_equals_single_launch():
             ctx.close()
     for a, b in zip(res[0], res[1]):
         torch.testing.assert_close(a, b, rtol=1e-4, atol=1e-5)
+
+
+def test_removed_step_apply_shim():
+    """The fused step + apply was removed; its two entry points stay as shims on a live trainer:
+    switching it off is accepted, switching it on is PT_ENOTSUP (6) with a message that says so, and the getter reports
+    that it did not run."""
+    ctx = _Ctx(31)
+    try:
+        assert ctx.L.pt_trainer_set_step_apply(ctx.t, 0) == 0
+        assert ctx.L.pt_trainer_step_apply(ctx.t) == 0
+        assert ctx.L.pt_trainer_set_step_apply(ctx.t, 1) == 6
+        msg = ctx.L.pt_last_error().decode()
+        assert "removed" in msg and "DESIGN" in msg, msg
+        assert ctx.L.pt_trainer_step_apply(ctx.t) == 0
+    finally:
+        ctx.close()

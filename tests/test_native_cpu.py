@@ -384,3 +384,15 @@ def test_universe_team_width_shim():
         msg = L.pt_last_error().decode()
         assert "removed" in msg and "DESIGN" in msg, msg
         assert L.pt_get_universe_team_width() == 1
+
+
+def test_removed_step_apply_shim_without_trainer():
+    """The removed fused step + apply's setter answers PT_EINVAL (1) to a null trainer like every pt_trainer_* call
+    (the slot-scale setter among them), the getters 0."""
+    from openke import _native
+    L = _native.lib()
+    for on in (0, 1):
+        assert L.pt_trainer_set_step_apply(None, on) == 1
+        assert L.pt_trainer_set_slot_scale(None, on) == 1
+    assert L.pt_trainer_step_apply(None) == 0
+    assert L.pt_trainer_slot_scale(None) == 0
