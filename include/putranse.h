@@ -147,10 +147,11 @@ int pt_trainer_last_path(const pt_trainer *t);
  * for a null trainer); the getter returns 0. */
 int pt_trainer_set_step_apply(pt_trainer *t, int32_t on);
 int pt_trainer_step_apply(const pt_trainer *t);
-/* slot-scale mode (opt-in; TransE float4 rows on the counting-sort path): the step stores per (positive, negative)
- * slot a record (positive, side, one scalar) and per positive its three normalized rows instead of the corrupted
- * entity's gradient row, and the apply pass re-forms each slot's row from them and the entity's own row
- * (CsrWork::slot_scale). pt_trainer_slot_scale: 1 when the current workspace is carved for it. */
+/* SHIM of a removed opt-in mode, the slot-scale mode of the large-neg TransE step (a record per slot and three
+ * normalized rows per positive instead of the corrupted entities' gradient rows, re-formed by the apply pass;
+ * measured slower than stored rows and removed: DESIGN.md section 4), kept so that callers which switch it off or
+ * ask whether it ran keep working. The setter accepts on = 0 (PT_OK) and answers PT_ENOTSUP to anything else
+ * (PT_EINVAL for a null trainer); the getter returns 0. */
 int pt_trainer_set_slot_scale(pt_trainer *t, int32_t on);
 int pt_trainer_slot_scale(const pt_trainer *t);
 /* Sample `calls` consecutive steps into the counting-sort batch layout the large-neg step kernels read,

@@ -52,11 +52,6 @@ struct ApplyParams {
     float margin, inv_count;
     int dbg;   // timing experiments only (PT_STEP_DBG bit 3: contribution rows read from a 4096-row hot window)
     int loss_assign;
-    // slot-scale mode (CsrWork::slot_scale): the step's slot records and positive base rows, the model's p and
-    // norm_flag (k_apply_buf<..., true>)
-    const int2 *srec;
-    const float *bases;
-    int p_norm, norm_flag;
 };
 
 // block 0, first wave: advance the sampler streams and reduce the step's loss partials in a fixed
@@ -156,7 +151,7 @@ __global__ __launch_bounds__(256) void k_apply(ApplyParams A) {
 // loads return; a bucket's contribution rows stream NC at a time with out-of-range offsets past its
 // end (the hardware returns zeros, so the adds need no branches), summed in bucket order after the
 // row's own gradient row.
-template <int G, int VEC, int KCH, int NC, int RPW, bool SC = false>
+template <int G, int VEC, int KCH, int NC, int RPW>
 __global__ __launch_bounds__(256) void k_apply_buf(ApplyParams A) {
     using Vec = V<G, VEC, KCH>;
     constexpr int GPB = 256 / G;
@@ -205,49 +200,6 @@ __global__ __launch_bounds__(256) void k_apply_buf(ApplyParams A) {
         bload(g[u], make_rsrc(T.grad, (uint32_t)T.rows * rowb), flag[u] ? (uint32_t)row[u] * rowb : kOob, D, lane);
         len = c1[u] - c0[u] > len ? c1[u] - c0[u] : len;
     }
-    if constexpr (SC) {
-#pragma clang fp contract(off)   // (k v and the sum stay two roundings, as the stored row and its add were)
-        // slot-scale mode (CsrWork::slot_scale): each slot's row re-formed from its record and its positive's
-        // normalized rows with the step kernel's own operations - e-hat = normalize(x) (fast form), v = b-hat - e-hat
-        // (a corrupted tail) or (e-hat + r-hat) - t-hat (a corrupted head), then k v (p = 2) or k sign(v) (p = 1)
-        // - and summed in bucket order: the bits the stored contribution rows held
-        const auto b_rs = make_rsrc(A.bases, 0x7fffffffu);
-#pragma unroll
-        for (int u = 0; u < RPW; ++u) {
-            if (!live[u] || ti[u] != 0 || c0[u] == c1[u]) continue;
-            Vec eh;
-            if (A.norm_flag) vnormalize<true>(x[u], eh); else eh = x[u];
-            for (int j = c0[u]; j < c1[u]; j += NC) {
-                int2 rc[NC];
-#pragma unroll
-                for (int q = 0; q < NC; ++q) {
-                    const int2 r = j + q < c1[u] ? A.srec[j + q] : make_int2(0, 0);
-                    rc[q] = make_int2(uni<G>(r.x), uni<G>(r.y));
-                }
-                Vec ra[NC], rb[NC];
-#pragma unroll
-                for (int q = 0; q < NC; ++q) {
-                    const bool ok = j + q < c1[u];
-                    const uint32_t pb = (uint32_t)(rc[q].x >> 1) * 3u;
-                    const bool tail = rc[q].x & 1;
-                    bload(ra[q], b_rs, ok ? (tail ? pb : pb + 1u) * rowb : kOob, D, lane);
-                    bload(rb[q], b_rs, ok && !tail ? (pb + 2u) * rowb : kOob, D, lane);
-                }
-#pragma unroll
-                for (int q = 0; q < NC; ++q) {
-                    if (j + q >= c1[u]) break;
-                    const bool tail = rc[q].x & 1;
-                    const float kk = __int_as_float(rc[q].y);
-#pragma unroll
-                    for (int i = 0; i < Vec::N; ++i) {
-                        const float vk = tail ? ra[q].x[i] - eh.x[i] : (eh.x[i] + ra[q].x[i]) - rb[q].x[i];
-                        const float gs = A.p_norm == 1 ? (vk > 0.f ? kk : (vk < 0.f ? -kk : 0.f)) : vk * kk;
-                        g[u].x[i] += gs;
-                    }
-                }
-            }
-        }
-    } else {
     // contribution rows (entity table only): the rows' buckets streamed side by side, NC per row at a
     // time, out-of-range past each bucket's end (zeros), summed in bucket order
     const auto c_rs = make_rsrc(A.t[0].contrib, 0x7fffffffu);
@@ -267,7 +219,6 @@ __global__ __launch_bounds__(256) void k_apply_buf(ApplyParams A) {
             for (int q = 0; q < NC; ++q)
 #pragma unroll
                 for (int i = 0; i < Vec::N; ++i) g[u].x[i] += c[u][q].x[i];
-    }
     }
 #pragma unroll
     for (int u = 0; u < RPW; ++u) {
@@ -302,114 +253,6 @@ __global__ __launch_bounds__(256) void k_apply_buf(ApplyParams A) {
     }
 }
 
-// Apply pass, RPW consecutive rows per lane group with all their loads in flight together (the
-// one-row-per-group form is a chain of two dependent memory round trips per row). Consecutive entity
-// rows own consecutive counting-sort contribution ranges, so a group streams ONE contiguous range
-// [start[r0], start[r0 + RPW]) and adds each contribution to its row.
-template <int G, int VEC, int KCH, int RPW>
-__global__ __launch_bounds__(256) void k_apply_rows(ApplyParams A) {
-    using Vec = V<G, VEC, KCH>;
-    constexpr int GPB = 256 / G;
-    const int lane = threadIdx.x % G;
-    const int64_t gi = (int64_t)blockIdx.x * GPB + threadIdx.x / G;
-    if (blockIdx.x == 0 && threadIdx.x < 64) apply_block0(A);
-    const int D = (int)A.dim;
-    int ti[RPW];
-    int64_t row[RPW];
-    int flag[RPW], c0[RPW], c1[RPW];
-    bool live[RPW];
-#pragma unroll
-    for (int u = 0; u < RPW; ++u) {
-        int64_t r = gi * RPW + u;
-        int t = 0;
-        while (t < A.ntab && r >= A.t[t].rows) {
-            r -= A.t[t].rows;
-            ++t;
-        }
-        ti[u] = t;
-        row[u] = r;
-        flag[u] = 0;
-        c0[u] = c1[u] = 0;
-        if (t < A.ntab) {
-            flag[u] = A.t[t].flag[r];
-            if (A.t[t].start) {
-                c0[u] = A.t[t].start[r];
-                c1[u] = A.t[t].start[r + 1];
-            }
-        }
-        live[u] = t < A.ntab && (flag[u] || c0[u] != c1[u]);
-    }
-    Vec x[RPW], g[RPW], a[RPW];
-#pragma unroll
-    for (int u = 0; u < RPW; ++u) {
-        if (!live[u]) continue;
-        const ApplyTable &T = A.t[ti[u]];
-        vload(x[u], T.w + row[u] * D, D, lane);
-        if (flag[u]) vload(g[u], T.grad + row[u] * D, D, lane); else vzero(g[u]);
-        if (A.opt != 0) vload(a[u], T.acc + row[u] * D, D, lane);
-    }
-    // the group's contribution range (entity table rows only carry contributions)
-    int cs = 0, ce = 0;
-    bool any = false;
-#pragma unroll
-    for (int u = 0; u < RPW; ++u) {
-        if (c0[u] == c1[u]) continue;
-        if (!any) cs = c0[u];
-        ce = c1[u];
-        any = true;
-    }
-    if (any) {
-        const float *contrib = A.t[0].contrib;
-        for (int j = cs; j < ce; j += 4) {
-            Vec c[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (j + q < ce) vload(c[q], contrib + (int64_t)(j + q) * D, D, lane);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (j + q >= ce) break;
-#pragma unroll
-                for (int u = 0; u < RPW; ++u) {
-                    if (j + q >= c0[u] && j + q < c1[u]) {
-#pragma unroll
-                        for (int i = 0; i < Vec::N; ++i) g[u].x[i] += c[q].x[i];
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < RPW; ++u) {
-        if (!live[u]) continue;
-        const ApplyTable &T = A.t[ti[u]];
-        Vec gg;
-        if (T.jacobian) {
-            const float n = sqrtf(vdot(x[u], x[u]));
-            vnormalize_bwd(x[u], n, g[u], gg);
-        } else {
-            gg = g[u];
-        }
-        if (A.opt == 0) {
-#pragma unroll
-            for (int i = 0; i < Vec::N; ++i) x[u].x[i] = x[u].x[i] + (-A.lr) * gg.x[i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < Vec::N; ++i) {
-                a[u].x[i] = a[u].x[i] + gg.x[i] * gg.x[i];
-                x[u].x[i] = x[u].x[i] + (-A.lr) * gg.x[i] / (sqrtf(a[u].x[i]) + 1e-10f);
-            }
-            vstore(a[u], T.acc + row[u] * D, D, lane);
-        }
-        vstore(x[u], T.w + row[u] * D, D, lane);
-        if (flag[u]) {
-            Vec z;
-            vzero(z);
-            vstore(z, T.grad + row[u] * D, D, lane);
-            if (lane == 0) T.flag[row[u]] = 0;
-        }
-    }
-}
-
 }  // namespace dev
 
 // ==================================================================== host launchers ===========
@@ -437,11 +280,6 @@ hipError_t launch_apply(const StepParams &P, const StepWorkspace &W, uint64_t *s
     A.inv_count = P.inv_count;
     A.dbg = P.dbg;
     A.loss_assign = P.loss_assign;
-    const bool sc = csr && csr->slot_scale;
-    A.srec = sc ? csr->srec : nullptr;
-    A.bases = sc ? csr->bases : nullptr;
-    A.p_norm = P.p_norm;
-    A.norm_flag = P.norm_flag;
     int64_t rows = 0;
     for (int i = 0; i < A.ntab; ++i) rows += A.t[i].rows;
     // float4 rows through raw buffers (PT_APPLY_OLD=1 keeps the kernels below)
@@ -467,10 +305,7 @@ hipError_t launch_apply(const StepParams &P, const StepWorkspace &W, uint64_t *s
         const dim3 grid((unsigned)((groups + gpb4 - 1) / gpb4)), block(256);
 #define PT_APPLYB(G_, K_, N_, R_)                                                              \
         if (G == G_ && KCH == K_ && nc == N_ && rpw == R_) {                                  \
-            if (sc)                                                                             \
-                hipLaunchKernelGGL((dev::k_apply_buf<G_, 4, K_, N_, R_, true>), grid, block, 0, st, A); \
-            else                                                                                \
-                hipLaunchKernelGGL((dev::k_apply_buf<G_, 4, K_, N_, R_>), grid, block, 0, st, A); \
+            hipLaunchKernelGGL((dev::k_apply_buf<G_, 4, K_, N_, R_>), grid, block, 0, st, A); \
             return hipGetLastError();                                                         \
         }
         PT_APPLYB(2, 1, 4, 1) PT_APPLYB(4, 1, 4, 1) PT_APPLYB(8, 1, 4, 1) PT_APPLYB(16, 1, 4, 1)
@@ -479,26 +314,7 @@ hipError_t launch_apply(const StepParams &P, const StepWorkspace &W, uint64_t *s
         PT_APPLYB(64, 1, 2, 4) PT_APPLYB(64, 1, 1, 4)
 #undef PT_APPLYB
     }
-    if (sc) return hipErrorInvalidValue;   // slot records are read only by k_apply_buf
     const int64_t gpb = 256 / s.G;
-    // PT_APPLY_RPW=2|4: several rows per lane group with one contribution stream (measured slower on
-    // C2: 20.4 / 22.0 us vs 16.8 us for one row per group, which stays the default)
-    const char *rpw_env = pt_tuning_env("PT_APPLY_RPW");
-    const int rpw = rpw_env ? atoi(rpw_env) : 1;
-    if (rpw == 4 || rpw == 2) {
-        const int64_t groups = (rows + rpw - 1) / rpw;
-        const dim3 grid((unsigned)((groups + gpb - 1) / gpb)), block(256);
-#define PT_APPLY4(G_, V_, K_)                                                                 \
-        if (s.G == G_ && s.VEC == V_ && s.KCH == K_) {                                      \
-            if (rpw == 4)                                                                   \
-                hipLaunchKernelGGL((dev::k_apply_rows<G_, V_, K_, 4>), grid, block, 0, st, A); \
-            else                                                                            \
-                hipLaunchKernelGGL((dev::k_apply_rows<G_, V_, K_, 2>), grid, block, 0, st, A); \
-            return hipGetLastError();                                                       \
-        }
-        PT_SHAPES(PT_APPLY4)
-#undef PT_APPLY4
-    }
     const dim3 grid((unsigned)((rows + gpb - 1) / gpb)), block(256);
 #define PT_APPLY(G_, V_, K_)                                                                  \
     if (s.G == G_ && s.VEC == V_ && s.KCH == K_) {                                          \

@@ -337,9 +337,7 @@ __device__ __forceinline__ int32_t gbcast(int32_t v, int j) {
     if constexpr (G == 64) return __builtin_amdgcn_readlane(v, j); else return __shfl(v, j, G);
 }
 
-// SC: the slot-scale mode (CsrWork::slot_scale) as its own instantiation - its branches inside the default
-// kernel had cost 1.5-2 us per C2 step (same-box A/B, tools_gpu/r05_ac.sh)
-template <int G, int VEC, int KCH, int NCH, int S, int PN, int NT = 256, bool SC = false>
+template <int G, int VEC, int KCH, int NCH, int S, int PN, int NT = 256>
 __global__ __launch_bounds__(NT) void k_step_csr(StepParams P, GlobalSink sink, CsrWork cw) {
     using Vec = V<G, VEC, KCH>;
     constexpr int GPB = NT / G;      // lane groups per block
@@ -412,13 +410,6 @@ __global__ __launch_bounds__(NT) void k_step_csr(StepParams P, GlobalSink sink, 
             vpos.x[i] = bt.x[i] - th.x[i];
         }
         ps = vpnorm<true>(vpos, p);
-        constexpr bool scale_mode = SC;
-        if (scale_mode && sub == 0) {   // the positive's normalized rows, for the apply pass to re-form slot rows
-            const auto base_rs = make_rsrc(cw.bases, (uint32_t)(P.batch_size * 3) * rowb);
-            bstore(bt, base_rs, (uint32_t)(b * 3) * rowb, D, lane);
-            bstore(rh, base_rs, (uint32_t)(b * 3 + 1) * rowb, D, lane);
-            bstore(th, base_rs, (uint32_t)(b * 3 + 2) * rowb, D, lane);
-        }
         auto process = [&](Vec(&E)[NCH], int k0) {
 #pragma unroll
             for (int u = 0; u < NCH; ++u) {
@@ -429,23 +420,12 @@ __global__ __launch_bounds__(NT) void k_step_csr(StepParams P, GlobalSink sink, 
                 const bool tail_side = r & 1;
                 Vec eh, vk, gs;
                 if (nf) vnormalize<true>(E[u], eh); else eh = E[u];
-                if constexpr (SC) {
-#pragma clang fp contract(off)   // e-hat's product stays rounded: k_apply_buf's slot-scale mode re-forms v the same way
-                    if (tail_side) {
+                if (tail_side) {
 #pragma unroll
-                        for (int i = 0; i < Vec::N; ++i) vk.x[i] = bt.x[i] - eh.x[i];
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < Vec::N; ++i) vk.x[i] = (eh.x[i] + rh.x[i]) - th.x[i];
-                    }
+                    for (int i = 0; i < Vec::N; ++i) vk.x[i] = bt.x[i] - eh.x[i];
                 } else {
-                    if (tail_side) {
 #pragma unroll
-                        for (int i = 0; i < Vec::N; ++i) vk.x[i] = bt.x[i] - eh.x[i];
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < Vec::N; ++i) vk.x[i] = (eh.x[i] + rh.x[i]) - th.x[i];
-                    }
+                    for (int i = 0; i < Vec::N; ++i) vk.x[i] = (eh.x[i] + rh.x[i]) - th.x[i];
                 }
                 const float ns = vpnorm<true>(vk, p);
                 const float a = uni<G>(ps - ns);
@@ -455,15 +435,7 @@ __global__ __launch_bounds__(NT) void k_step_csr(StepParams P, GlobalSink sink, 
                 // slot gradient d loss / d e-hat: -g for a corrupted tail, +g for a corrupted head
                 // (g = dL/dv); an inactive pair stores zeros (the reserved slot must be defined)
                 vpnorm_bwd<true>(vk, ns, p, tail_side ? c : -c, gs);
-                if constexpr (scale_mode) {
-                    // the slot's record: its positive and side, and vpnorm_bwd's scalar (p = 2: ds / ns as the
-                    // fast form computes it, p = 1: ds) - the apply pass forms gs again from them
-                    const float ds = tail_side ? c : -c;
-                    const float kk = p == 1 ? ds : (ns == 0.f ? 0.f : ds * frcp<true>(ns));
-                    if (lane == 0) cw.srec[di] = make_int2((int32_t)(b << 1) | (tail_side ? 1 : 0), __float_as_int(kk));
-                } else {
-                    bstore(gs, con_rs, PT_ABLATE(P.dbg, 1) ? kOob : slot, D, lane);
-                }
+                bstore(gs, con_rs, PT_ABLATE(P.dbg, 1) ? kOob : slot, D, lane);
                 if (tail_side) {
 #pragma unroll
                     for (int i = 0; i < Vec::N; ++i) At.x[i] -= gs.x[i];
@@ -673,11 +645,7 @@ hipError_t launch_step(const StepParams &P, const DeviceGraph &g, const uint64_t
         if (G == G_ && KCH == K_ && nch == N_ && S == S_) {                                          \
             constexpr int NT_ = S_ * G_ >= 256 || 256 % (S_ * G_) != 0 ? S_ * G_ : 256;             \
             const dim3 grid((unsigned)((P.batch_size * S_ * G_ + NT_ - 1) / NT_)), block(NT_);        \
-            if (csr->slot_scale && P.p_norm == 1)                                                    \
-                hipLaunchKernelGGL((dev::k_step_csr<G_, 4, K_, N_, S_, 1, NT_, true>), grid, block, 0, st, P, sink, *csr); \
-            else if (csr->slot_scale)                                                                \
-                hipLaunchKernelGGL((dev::k_step_csr<G_, 4, K_, N_, S_, 2, NT_, true>), grid, block, 0, st, P, sink, *csr); \
-            else if (P.p_norm == 1)                                                                  \
+            if (P.p_norm == 1)                                                                       \
                 hipLaunchKernelGGL((dev::k_step_csr<G_, 4, K_, N_, S_, 1, NT_>), grid, block, 0, st, P, sink, *csr); \
             else                                                                                     \
                 hipLaunchKernelGGL((dev::k_step_csr<G_, 4, K_, N_, S_, 2, NT_>), grid, block, 0, st, P, sink, *csr); \

@@ -36,7 +36,6 @@ struct pt_trainer {
     pt::CsrWork csr{};
     int64_t csr_bs = 0, csr_neg = 0, csr_chunk = 0;   // layout the workspace was carved for
     bool csr_fused = false;                             // k_sample_sort plan fits LDS
-    bool slot_scale_on = false;                         // pt_trainer_set_slot_scale (CsrWork::slot_scale)
     bool csr_part = false;                              // k_sample_part prepared (its LDS limit raised)
     int last_path = -1;                                 // sampling path of the last enqueued chunk (PT_PATH_*)
     int64_t lpart_cap = 0;                             // W.lpart capacity (positives)
@@ -184,15 +183,6 @@ static int choose_path(const pt_trainer *t, int64_t calls, int64_t bs, int64_t n
     return PT_PATH_TWO_PASS;
 }
 
-// whether the slot-scale mode is wanted (pt_trainer_set_slot_scale; the tuning build's PT_SLOT_SCALE forces it)
-static bool slot_scale_wanted(const pt_trainer *t) {
-    static const int forced = [] {
-        const char *v = pt_tuning_env("PT_SLOT_SCALE");
-        return v ? atoi(v) : -1;
-    }();
-    return forced >= 0 ? forced != 0 : t->slot_scale_on;
-}
-
 // Workspace of the counting-sort path, carved once per (bs, neg): room for a chunk of pre-sampled
 // steps (<= kCsrChunk, fewer when a step's arrays are large) plus one step's gradient rows. A new
 // (bs, neg) re-carves it (and drops captured graphs, whose kernels hold the old pointers).
@@ -208,12 +198,7 @@ static int ensure_csr(pt_trainer *t, int64_t bs, int64_t neg) {
     const size_t a_pos = al(16 * bs * chunk), a_neg = al(4 * bs * neg * chunk), a_off = a_neg,
                  a_cnt = al(4 * cs * chunk), a_start = al(4 * ss * chunk), a_tick = al(4 * chunk + 4),
                  a_con = al(4 * bs * neg * D);
-    // slot-scale mode: the step's slot records and positive base rows take the contribution region's place
-    // (TransE float4 rows: the k_step_csr / k_apply_buf pair)
-    const bool scm = slot_scale_wanted(t) && t->P.model == 0 && D % 4 == 0;
-    const size_t a_srec = al(8 * bs * neg), a_bases = al(4 * bs * 3 * D);
-    const size_t need = a_pos + a_neg + a_off + a_cnt + a_start + a_tick +
-                        std::max(a_con, scm ? a_srec + a_bases : (size_t)0);
+    const size_t need = a_pos + a_neg + a_off + a_cnt + a_start + a_tick + a_con;
     // ---- (re)allocation
     PT_HIP(hipDeviceSynchronize());   // queued work may still use the old carving
     t->drop_graphs();
@@ -234,9 +219,6 @@ static int ensure_csr(pt_trainer *t, int64_t bs, int64_t neg) {
     t->csr.start = (int32_t *)b; b += a_start;
     t->csr.tick = (int32_t *)b; b += a_tick;
     t->csr.contrib = (float *)b;
-    t->csr.slot_scale = scm ? 1 : 0;
-    t->csr.srec = scm ? (int2 *)b : nullptr;
-    t->csr.bases = scm ? (float *)(b + a_srec) : nullptr;
     t->csr.cnt_stride = cs;
     t->csr.start_stride = ss;
     t->csr_bs = bs;
@@ -446,14 +428,13 @@ static int ensure_lpart(pt_trainer *t, int64_t bs) {
     return PT_OK;
 }
 
-static int prepare_sampled(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, int64_t steps) {
+static int prepare_sampled(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg) {
     int rc = check_step_args(t->P, s, bs, neg);
     if (rc) return rc;
     rc = ensure_lpart(t, bs);
     if (rc) return rc;
     rc = s->g->upload();
     if (rc) return rc;
-    (void)steps;
     if (use_csr(neg)) return ensure_csr(t, bs, neg);
     return PT_OK;
 }
@@ -564,7 +545,7 @@ extern "C" int pt_trainer_step(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t
     }
     PT_CHECK(bs > 0 && neg > 0, PT_EINVAL, "batch_size and neg_ent must be positive");
     if (t->ordered) return enqueue_ordered_run(t, s, bs, neg, bern, filter, 1, d_loss, 0, (hipStream_t)stream);
-    int rc = prepare_sampled(t, s, bs, neg, 1);
+    int rc = prepare_sampled(t, s, bs, neg);
     if (rc) return rc;
     return enqueue_run(t, s, bs, neg, bern, filter, 1, d_loss, (hipStream_t)stream);
 }
@@ -576,7 +557,7 @@ extern "C" int pt_trainer_run_timed(pt_trainer *t, pt_sampler *s, int64_t bs, in
                                     int64_t filter, int64_t steps, float *d_losses, float *ms4, void *stream) {
     PT_CHECK(t && ms4 && steps > 0, PT_EINVAL, "pt_trainer_run_timed: bad argument");
     PT_CHECK(!t->ordered, PT_ENOTSUP, "pt_trainer_run_timed times the fast path (reference-order mode is on)");
-    int rc = prepare_sampled(t, s, bs, neg, steps);
+    int rc = prepare_sampled(t, s, bs, neg);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     Timing tm;
@@ -693,9 +674,9 @@ extern "C" int pt_trainer_run_timed(pt_trainer *t, pt_sampler *s, int64_t bs, in
     return PT_OK;
 }
 
-// Shim of the removed fused step + apply (an opt-in mode measured slower than the k_step_csr + k_apply_buf pair,
-// DESIGN.md §4), kept for callers that switch it off or ask whether it ran: 0 is accepted, anything else is
-// PT_ENOTSUP, and the getter reports 0
+// Shims of the removed fused step + apply and slot-scale mode (opt-in modes measured slower than the k_step_csr +
+// k_apply_buf pair), kept for callers that switch them off or ask whether they ran: 0 is accepted,
+// anything else is PT_ENOTSUP, and the getters report 0
 extern "C" int pt_trainer_set_step_apply(pt_trainer *t, int32_t on) {
     PT_CHECK(t, PT_EINVAL, "null trainer");
     PT_CHECK(!on, PT_ENOTSUP,
@@ -706,12 +687,11 @@ extern "C" int pt_trainer_step_apply(const pt_trainer *) { return 0; }
 
 extern "C" int pt_trainer_set_slot_scale(pt_trainer *t, int32_t on) {
     PT_CHECK(t, PT_EINVAL, "null trainer");
-    if (t->slot_scale_on != (on != 0)) t->csr_bs = 0;   // re-carve the workspace (slot records / base rows)
-    t->slot_scale_on = on != 0;
-    t->drop_graphs();
+    PT_CHECK(!on, PT_ENOTSUP,
+             "pt_trainer_set_slot_scale: the slot-scale mode was removed (measured slower, DESIGN.md §4)");
     return PT_OK;
 }
-extern "C" int pt_trainer_slot_scale(const pt_trainer *t) { return t && t->csr.slot_scale ? 1 : 0; }
+extern "C" int pt_trainer_slot_scale(const pt_trainer *) { return 0; }
 
 extern "C" int pt_trainer_last_path(const pt_trainer *t) { return t ? t->last_path : -1; }
 
@@ -721,7 +701,7 @@ extern "C" int pt_trainer_sample_csr(pt_trainer *t, pt_sampler *s, int64_t bs, i
     PT_CHECK(t && s && h_pos && h_neg && h_dst && h_start, PT_EINVAL, "pt_trainer_sample_csr: null argument");
     PT_CHECK(calls > 0, PT_EINVAL, "pt_trainer_sample_csr: calls must be positive");
     PT_CHECK(path >= -1 && path <= PT_PATH_PART, PT_EINVAL, "pt_trainer_sample_csr: path must be -1 or PT_PATH_*");
-    int rc = prepare_sampled(t, s, bs, neg, calls);
+    int rc = prepare_sampled(t, s, bs, neg);
     if (rc) return rc;
     if (!t->csr_block) {   // small neg runs the in-step sampler; carve the counting-sort workspace anyway
         rc = ensure_csr(t, bs, neg);
@@ -771,7 +751,7 @@ extern "C" int pt_trainer_run(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t 
         PT_CHECK(bs > 0 && neg > 0, PT_EINVAL, "batch_size and neg_ent must be positive");
         return enqueue_ordered_run(t, s, bs, neg, bern, filter, steps, d_losses, 1, (hipStream_t)stream);
     }
-    int rc = prepare_sampled(t, s, bs, neg, steps);
+    int rc = prepare_sampled(t, s, bs, neg);
     if (rc) return rc;
     GraphKey key{s, s->g->dev.rec, d_losses, s->d_states, bs, neg, bern, filter, steps};
     auto it = t->graphs.find(key);

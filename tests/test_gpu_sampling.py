@@ -17,8 +17,9 @@ the apply pass only sums a bucket.)
 Shapes follow the reference's step: the k-th negative of positive b is slot b*neg + k (the reference's
 (k+1)*bs + b, Base.cpp:216-232). Cases cover >= 96 calls per chunk, slot counts that are neither a
 multiple of the 1024/512-thread strides nor divided by neg (bs 200, neg 13: the second lock-step slot,
-the incremental (b, k) carry), neg > 1024 (db == 0), filter = 0 and bern = 0, and bs*neg >= 65536 (the
-split sampler's unpacked 32-bit counts).
+the incremental (b, k) carry), neg > 1024 (db == 0), filter = 0 and bern = 0, bs*neg >= 65536 (the
+split sampler's unpacked 32-bit counts), and short chunks (6, 9 and 20 calls: the split sampler's automatic part
+counts).
 """
 import ctypes
 
@@ -112,6 +113,10 @@ CASES = [
     (200, 13, 0, 0, 100, 7),     # no filter, no bern
     (37, 1100, 1, 1, 4, 9),      # neg > 1024: db == 0 in the slot walk
     (3000, 25, 1, 1, 3, 11),     # 75,000 slots per call: the split sampler's 32-bit counts
+    # the split sampler's automatic part counts of short chunks: ceil(512 / calls) = 26, 86 and 57 parts
+    (200, 13, 1, 1, 20, 17),
+    (3000, 25, 1, 1, 6, 19),
+    (200, 13, 0, 0, 9, 23),
 ]
 
 
@@ -212,5 +217,21 @@ def test_removed_step_apply_shim():
         msg = ctx.L.pt_last_error().decode()
         assert "removed" in msg and "DESIGN" in msg, msg
         assert ctx.L.pt_trainer_step_apply(ctx.t) == 0
+    finally:
+        ctx.close()
+
+
+def test_removed_slot_scale_shim():
+    """The slot-scale mode was removed; its two entry points stay as shims on a live trainer:
+    switching it off is accepted, switching it on is PT_ENOTSUP (6) with a message that says so, and the getter reports
+    that it did not run."""
+    ctx = _Ctx(37)
+    try:
+        assert ctx.L.pt_trainer_set_slot_scale(ctx.t, 0) == 0
+        assert ctx.L.pt_trainer_slot_scale(ctx.t) == 0
+        assert ctx.L.pt_trainer_set_slot_scale(ctx.t, 1) == 6
+        msg = ctx.L.pt_last_error().decode()
+        assert "removed" in msg and "DESIGN" in msg, msg
+        assert ctx.L.pt_trainer_slot_scale(ctx.t) == 0
     finally:
         ctx.close()

@@ -388,11 +388,13 @@ def test_universe_team_width_shim():
 
 def test_removed_step_apply_shim_without_trainer():
     """The removed fused step + apply's setter answers PT_EINVAL (1) to a null trainer like every pt_trainer_* call
-    (the slot-scale setter among them), the getters 0."""
+    (the shim of the removed slot-scale mode and pt_trainer_set_sample_split among them), the getters 0."""
     from openke import _native
     L = _native.lib()
     for on in (0, 1):
         assert L.pt_trainer_set_step_apply(None, on) == 1
         assert L.pt_trainer_set_slot_scale(None, on) == 1
+    for h in (-2, -1, 0, 2):
+        assert L.pt_trainer_set_sample_split(None, h) == 1
     assert L.pt_trainer_step_apply(None) == 0
     assert L.pt_trainer_slot_scale(None) == 0
