@@ -114,9 +114,11 @@ int pt_trainer_run(pt_trainer *t, pt_sampler *sampler, int64_t bs, int64_t neg, 
  * sampler); parts = workgroups per call of the split sampler (0 = automatic, ceil(512 / calls)). Every path
  * draws the same batches (bit-exact); this selects only how. */
 int pt_trainer_set_sampling(pt_trainer *t, int32_t path, int64_t parts);
-/* Split-sampler chunks sampled in two launches (same batches, bit-exact): the first `head` steps ahead of the
- * first step, the rest on the trainer's side stream alongside the first steps' training. head = 0 or -1 (the
- * default): one launch (measured faster); a chunk of <= head steps is sampled in one launch. */
+/* Two-launch split sampling. Training (pt_trainer_run) no longer uses it: sampling a chunk's first `head` steps
+ * ahead and the rest on a side stream beside the first steps' training was measured slower,
+ * and every chunk of a run is sampled by one launch. The setter still selects how pt_trainer_sample_csr samples a
+ * PT_PATH_PART chunk (same batches, bit-exact): `head` calls by one launch, the rest by a second on the trainer's
+ * side stream. head = 0 or -1 (the default): one launch; a chunk of <= head calls is sampled in one launch. */
 int pt_trainer_set_sample_split(pt_trainer *t, int64_t head);
 /* Reference-order (deterministic) mode of a trainer: every later pt_trainer_step / pt_trainer_run sums each
  * table row's gradient in slot order, lookup by lookup (batch_h, batch_t, batch_r; norm_vector(batch_r)),

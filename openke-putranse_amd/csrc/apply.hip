@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void k_apply(ApplyParams A) {
 // loads return; a bucket's contribution rows stream NC at a time with out-of-range offsets past its
 // end (the hardware returns zeros, so the adds need no branches), summed in bucket order after the
 // row's own gradient row.
-template <int G, int VEC, int KCH, int NC, int RPW>
+template <int G, int VEC, int KCH, int NC>
 __global__ __launch_bounds__(256) void k_apply_buf(ApplyParams A) {
     using Vec = V<G, VEC, KCH>;
     constexpr int GPB = 256 / G;
@@ -160,95 +160,84 @@ __global__ __launch_bounds__(256) void k_apply_buf(ApplyParams A) {
     if (blockIdx.x == 0 && threadIdx.x < 64) apply_block0(A);
     const int D = (int)A.dim;
     const uint32_t rowb = (uint32_t)D * 4u;
-    // RPW consecutive rows per group, every load of all of them in flight together
-    int ti[RPW], flag[RPW], c0[RPW], c1[RPW];
-    int64_t row[RPW];
-    bool live[RPW];
-    Vec x[RPW], g[RPW], a[RPW];
-#pragma unroll
-    for (int u = 0; u < RPW; ++u) {
-        int64_t r = gi * RPW + u;
-        int t = 0;
-        while (t < A.ntab && r >= A.t[t].rows) {
-            r -= A.t[t].rows;
-            ++t;
-        }
-        ti[u] = t;
-        row[u] = r;
-        live[u] = t < A.ntab;
-        flag[u] = 0;
-        c0[u] = c1[u] = 0;
+    // the group's row: its table and the row inside it
+    int64_t row = gi;
+    int ti = 0;
+    while (ti < A.ntab && row >= A.t[ti].rows) {
+        row -= A.t[ti].rows;
+        ++ti;
     }
+    const bool live = ti < A.ntab;
+    int flag = 0, c0 = 0, c1 = 0;
+    Vec x, g, a;
+    // (the one-trip loops keep the instruction stream of the former rows-per-group loops: DESIGN.md §4)
+    // ---- every load of the row in flight together
 #pragma unroll
-    for (int u = 0; u < RPW; ++u) {
-        if (!live[u]) continue;
-        const ApplyTable &T = A.t[ti[u]];
+    for (int once = 0; once < 1; ++once) {
+        if (!live) continue;
+        const ApplyTable &T = A.t[ti];
         const uint32_t tb = (uint32_t)T.rows * rowb;
-        bload(x[u], make_rsrc(T.w, tb), (uint32_t)row[u] * rowb, D, lane);
-        if (A.opt != 0) bload(a[u], make_rsrc(T.acc, tb), (uint32_t)row[u] * rowb, D, lane);
-        flag[u] = T.flag[row[u]];
+        bload(x, make_rsrc(T.w, tb), (uint32_t)row * rowb, D, lane);
+        if (A.opt != 0) bload(a, make_rsrc(T.acc, tb), (uint32_t)row * rowb, D, lane);
+        flag = T.flag[row];
         if (T.start) {
-            c0[u] = T.start[row[u]];
-            c1[u] = T.start[row[u] + 1];
+            c0 = T.start[row];
+            c1 = T.start[row + 1];
         }
     }
     int len = 0;
 #pragma unroll
-    for (int u = 0; u < RPW; ++u) {
-        if (!live[u]) continue;
-        const ApplyTable &T = A.t[ti[u]];
-        bload(g[u], make_rsrc(T.grad, (uint32_t)T.rows * rowb), flag[u] ? (uint32_t)row[u] * rowb : kOob, D, lane);
-        len = c1[u] - c0[u] > len ? c1[u] - c0[u] : len;
+    for (int once = 0; once < 1; ++once) {
+        if (!live) continue;
+        const ApplyTable &T = A.t[ti];
+        bload(g, make_rsrc(T.grad, (uint32_t)T.rows * rowb), flag ? (uint32_t)row * rowb : kOob, D, lane);
+        len = c1 - c0 > len ? c1 - c0 : len;
     }
-    // contribution rows (entity table only): the rows' buckets streamed side by side, NC per row at a
-    // time, out-of-range past each bucket's end (zeros), summed in bucket order
+    // ---- contribution rows (entity table only): the row's bucket streamed NC at a time, out-of-range past
+    // the bucket's end (zeros), summed in bucket order
     const auto c_rs = make_rsrc(A.t[0].contrib, 0x7fffffffu);
     for (int j = 0; j < len; j += NC) {
-        Vec c[RPW][NC];
+        Vec c[NC];
 #pragma unroll
-        for (int u = 0; u < RPW; ++u)
+        for (int q = 0; q < NC; ++q)
+            bload(c[q], c_rs,
+                  c0 + j + q < c1 ? (uint32_t)(PT_ABLATE(A.dbg, 8) ? (c0 + j + q) & 4095 : c0 + j + q) * rowb : kOob, D,
+                  lane);
 #pragma unroll
-            for (int q = 0; q < NC; ++q)
-                bload(c[u][q], c_rs,
-                      c0[u] + j + q < c1[u] ? (uint32_t)(PT_ABLATE(A.dbg, 8) ? (c0[u] + j + q) & 4095 : c0[u] + j + q) * rowb
-                                            : kOob,
-                      D, lane);
+        for (int q = 0; q < NC; ++q)
 #pragma unroll
-        for (int u = 0; u < RPW; ++u)
-#pragma unroll
-            for (int q = 0; q < NC; ++q)
-#pragma unroll
-                for (int i = 0; i < Vec::N; ++i) g[u].x[i] += c[u][q].x[i];
+            for (int i = 0; i < Vec::N; ++i) g.x[i] += c[q].x[i];
     }
+    // ---- the update
 #pragma unroll
-    for (int u = 0; u < RPW; ++u) {
-        if (!live[u] || (!flag[u] && c0[u] == c1[u])) continue;   // untouched row: unchanged
-        const ApplyTable &T = A.t[ti[u]];
+    for (int once = 0; once < 1; ++once) {
+        if (!live || (!flag && c0 == c1)) continue;   // untouched row: unchanged
+        const ApplyTable &T = A.t[ti];
         const uint32_t tb = (uint32_t)T.rows * rowb;
         Vec gg;
         if (T.jacobian) {
-            const float n = sqrtf(vdot(x[u], x[u]));
-            vnormalize_bwd(x[u], n, g[u], gg);
+            const float n = sqrtf(vdot(x, x));
+            vnormalize_bwd(x, n, g, gg);
         } else {
-            gg = g[u];
+            gg = g;
         }
         if (A.opt == 0) {
 #pragma unroll
-            for (int i = 0; i < Vec::N; ++i) x[u].x[i] = x[u].x[i] + (-A.lr) * gg.x[i];
+            for (int i = 0; i < Vec::N; ++i) x.x[i] = x.x[i] + (-A.lr) * gg.x[i];
         } else {
 #pragma unroll
             for (int i = 0; i < Vec::N; ++i) {
-                a[u].x[i] = a[u].x[i] + gg.x[i] * gg.x[i];
-                x[u].x[i] = x[u].x[i] + (-A.lr) * gg.x[i] / (sqrtf(a[u].x[i]) + 1e-10f);
+                a.x[i] = a.x[i] + gg.x[i] * gg.x[i];
+                x.x[i] = x.x[i] + (-A.lr) * gg.x[i] / (sqrtf(a.x[i]) + 1e-10f);
             }
-            bstore(a[u], make_rsrc(T.acc, tb), (uint32_t)row[u] * rowb, D, lane);
+            bstore(a, make_rsrc(T.acc, tb), (uint32_t)row * rowb, D, lane);
         }
-        bstore(x[u], make_rsrc(T.w, tb), (uint32_t)row[u] * rowb, D, lane);
-        if (flag[u]) {
+        bstore(x, make_rsrc(T.w, tb), (uint32_t)row * rowb, D, lane);
+        if (flag) {
             Vec z;
             vzero(z);
-            bstore(z, make_rsrc(T.grad, tb), (uint32_t)row[u] * rowb, D, lane);
-            if (lane == 0) T.flag[row[u]] = 0;
+            bstore(z, make_rsrc(T.grad, tb), (uint32_t)row * rowb, D, lane);
+            if (lane == 0) T.flag[row] = 0;
         }
     }
 }
@@ -282,36 +271,28 @@ hipError_t launch_apply(const StepParams &P, const StepWorkspace &W, uint64_t *s
     A.loss_assign = P.loss_assign;
     int64_t rows = 0;
     for (int i = 0; i < A.ntab; ++i) rows += A.t[i].rows;
-    // float4 rows through raw buffers (PT_APPLY_OLD=1 keeps the kernels below)
-    static const bool old_apply = [] {
-        const char *v = pt_tuning_env("PT_APPLY_OLD");
-        return v && atoi(v) != 0;
-    }();
+    // float4 rows through raw buffers where the offsets fit 31 bits, else the kernels below
     int64_t con_rows = 0;
     if (csr) con_rows = P.batch_size * P.neg;
     const bool fits31 = (P.ent_total + P.rel_total + con_rows) * P.dim * 4 < (int64_t(1) << 31);
-    if (P.dim % 4 == 0 && fits31 && !old_apply) {
+    if (P.dim % 4 == 0 && fits31) {
         const int64_t chunks = P.dim / 4;
         int G = 2;
         while (G < chunks && G < 64) G <<= 1;
         const int KCH = (int)((chunks + G - 1) / G);
         // contribution rows in flight per lane group: 8 for one-chunk float4 rows (C2: the bucket of a row
         // - Poisson, mean 3.6 at C2 - mostly in one round trip; measured 12.0 vs 12.6 us), else 4
-        int nc = G == 64 && KCH == 1 ? 8 : 4, rpw = 1;
-        if (const char *v = pt_tuning_env("PT_APPLY_NC")) nc = atoi(v);
-        if (const char *v = pt_tuning_env("PT_APPLY_RPW")) rpw = atoi(v);
+        const int nc = G == 64 && KCH == 1 ? 8 : 4;
         const int64_t gpb4 = 256 / G;
-        const int64_t groups = (rows + rpw - 1) / rpw;
-        const dim3 grid((unsigned)((groups + gpb4 - 1) / gpb4)), block(256);
-#define PT_APPLYB(G_, K_, N_, R_)                                                              \
-        if (G == G_ && KCH == K_ && nc == N_ && rpw == R_) {                                  \
-            hipLaunchKernelGGL((dev::k_apply_buf<G_, 4, K_, N_, R_>), grid, block, 0, st, A); \
-            return hipGetLastError();                                                         \
+        const dim3 grid((unsigned)((rows + gpb4 - 1) / gpb4)), block(256);
+#define PT_APPLYB(G_, K_, N_)                                                              \
+        if (G == G_ && KCH == K_ && nc == N_) {                                           \
+            hipLaunchKernelGGL((dev::k_apply_buf<G_, 4, K_, N_>), grid, block, 0, st, A); \
+            return hipGetLastError();                                                     \
         }
-        PT_APPLYB(2, 1, 4, 1) PT_APPLYB(4, 1, 4, 1) PT_APPLYB(8, 1, 4, 1) PT_APPLYB(16, 1, 4, 1)
-        PT_APPLYB(32, 1, 4, 1) PT_APPLYB(64, 1, 4, 1) PT_APPLYB(64, 2, 4, 1) PT_APPLYB(64, 3, 4, 1)
-        PT_APPLYB(64, 4, 4, 1) PT_APPLYB(64, 1, 2, 1) PT_APPLYB(64, 1, 4, 2) PT_APPLYB(64, 1, 2, 2) PT_APPLYB(64, 1, 8, 1)
-        PT_APPLYB(64, 1, 2, 4) PT_APPLYB(64, 1, 1, 4)
+        // every (G, KCH) of a supported dim (shape_supported: dim / 4 <= 128 chunks, so KCH <= 2)
+        PT_APPLYB(2, 1, 4) PT_APPLYB(4, 1, 4) PT_APPLYB(8, 1, 4) PT_APPLYB(16, 1, 4) PT_APPLYB(32, 1, 4)
+        PT_APPLYB(64, 1, 8) PT_APPLYB(64, 2, 4)
 #undef PT_APPLYB
     }
     const int64_t gpb = 256 / s.G;

@@ -1068,15 +1068,8 @@ hipError_t launch_sample_sort(const DeviceGraph &g, const uint64_t *states, int6
     return hipGetLastError();
 }
 
-// split sampler: threads per workgroup (PT_PART_NT = 256 | 512 | 1024 for tuning), LDS plan
-static int part_nt() {
-    static const int nt = [] {
-        const char *v = pt_tuning_env("PT_PART_NT");
-        const int x = v ? atoi(v) : 512;
-        return x == 256 || x == 1024 ? x : 512;
-    }();
-    return nt;
-}
+// split sampler: threads per workgroup, LDS plan
+static constexpr int kPartNT = 512;
 static bool part_pack(int64_t bs, int64_t neg) { return bs * neg < 65536; }
 static size_t sample_part_lds(int64_t bs, int64_t neg, int64_t n, int64_t parts) {
     const int64_t cw = part_pack(bs, neg) ? (n + 1) >> 1 : n;
@@ -1087,15 +1080,15 @@ static size_t sample_part_lds(int64_t bs, int64_t neg, int64_t n, int64_t parts)
 // lock-step slots per thread: 4 when a part holds >= 3 slots per thread, else 2
 static int part_sl(int64_t bs, int64_t neg, int64_t parts) {
     const int64_t per = (bs + parts - 1) / parts * neg;
-    return per >= 3 * part_nt() ? 4 : 2;
+    return per >= 3 * kPartNT ? 4 : 2;
 }
 
-template <int NT, bool PACK>
+template <bool PACK>
 static hipError_t part_attr() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dev::k_sample_part<NT, PACK, 2>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dev::k_sample_part<kPartNT, PACK, 2>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSampleSortLds);
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(dev::k_sample_part<NT, PACK, 4>),
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(dev::k_sample_part<kPartNT, PACK, 4>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSampleSortLds);
 }
 
@@ -1106,12 +1099,7 @@ bool sample_part_fits(int64_t bs, int64_t neg, int64_t n, int64_t parts) {
 
 bool sample_part_prepare(int64_t bs, int64_t neg, int64_t n, int64_t parts) {
     if (!sample_part_fits(bs, neg, n, parts)) return false;
-    const bool pk = part_pack(bs, neg);
-    switch (part_nt()) {
-        case 256: return (pk ? part_attr<256, true>() : part_attr<256, false>()) == hipSuccess;
-        case 1024: return (pk ? part_attr<1024, true>() : part_attr<1024, false>()) == hipSuccess;
-        default: return (pk ? part_attr<512, true>() : part_attr<512, false>()) == hipSuccess;
-    }
+    return (part_pack(bs, neg) ? part_attr<true>() : part_attr<false>()) == hipSuccess;
 }
 
 hipError_t launch_sample_part(const DeviceGraph &g, uint64_t *states, int64_t threads, int64_t bs, int64_t neg,
@@ -1123,15 +1111,13 @@ hipError_t launch_sample_part(const DeviceGraph &g, uint64_t *states, int64_t th
     const dim3 grid((unsigned)(calls * parts));
     const bool pk = part_pack(bs, neg);
     const int sl = part_sl(bs, neg, parts);
-#define PT_PART(NT_, PK_, SL_)                                                                                 \
-    if (part_nt() == NT_ && pk == PK_ && sl == SL_) {                                                        \
-        hipLaunchKernelGGL((dev::k_sample_part<NT_, PK_, SL_>), grid, dim3(NT_), lds, st, g, states, threads, \
-                           bs, neg, bern, filter, parts, w, call0, advance);                                  \
-        return hipGetLastError();                                                                            \
+#define PT_PART(PK_, SL_)                                                                                          \
+    if (pk == PK_ && sl == SL_) {                                                                                  \
+        hipLaunchKernelGGL((dev::k_sample_part<kPartNT, PK_, SL_>), grid, dim3(kPartNT), lds, st, g, states, threads, \
+                           bs, neg, bern, filter, parts, w, call0, advance);                                       \
+        return hipGetLastError();                                                                                  \
     }
-    PT_PART(256, true, 2) PT_PART(256, true, 4) PT_PART(256, false, 2) PT_PART(256, false, 4)
-    PT_PART(512, true, 2) PT_PART(512, true, 4) PT_PART(512, false, 2) PT_PART(512, false, 4)
-    PT_PART(1024, true, 2) PT_PART(1024, true, 4) PT_PART(1024, false, 2) PT_PART(1024, false, 4)
+    PT_PART(true, 2) PT_PART(true, 4) PT_PART(false, 2) PT_PART(false, 4)
 #undef PT_PART
     return hipErrorInvalidValue;
 }

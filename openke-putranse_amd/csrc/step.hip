@@ -567,28 +567,25 @@ int pick_nch(int64_t neg, int kch) {
     X(64, 1, 1, 1, 1) X(64, 1, 1, 4, 1) X(64, 1, 1, 8, 1) X(64, 1, 1, 8, 4) X(64, 1, 1, 32, 4)        \
     X(64, 1, 2, 1, 1) X(64, 1, 2, 4, 1) X(64, 1, 2, 8, 1) X(64, 1, 2, 8, 4) X(64, 1, 2, 32, 4)        \
     X(64, 1, 4, 1, 1) X(64, 1, 4, 4, 1) X(64, 1, 4, 8, 1) X(64, 1, 4, 8, 4) X(64, 1, 4, 32, 4)        \
-    X(64, 1, 4, 8, 2) X(64, 1, 4, 4, 4) X(64, 1, 4, 4, 2)                                             \
+    X(64, 1, 4, 4, 4)                                                                                 \
     X(64, 1, 8, 1, 1) X(64, 1, 8, 4, 1) X(64, 1, 8, 8, 1) X(64, 1, 8, 8, 4)
 
 }  // namespace
-// k_step_csr instances (G, KCH, NCH), float4 lanes
-#define PT_CSTEPS(X)                                                                                   \
-    X(2, 1, 2, 1) X(4, 1, 2, 1) X(8, 1, 2, 1) X(16, 1, 2, 1) X(32, 1, 2, 1) X(64, 1, 2, 1)                \
-    X(2, 1, 2, 2) X(4, 1, 2, 2) X(8, 1, 2, 2) X(16, 1, 2, 2) X(32, 1, 2, 2) X(64, 1, 2, 2)                \
-    X(2, 1, 2, 4) X(4, 1, 2, 4) X(8, 1, 2, 4) X(16, 1, 2, 4) X(32, 1, 2, 4) X(64, 1, 2, 4)                \
-    X(64, 1, 4, 4) X(64, 1, 1, 4) X(64, 2, 2, 1)             \
-    X(64, 2, 2, 2) X(64, 2, 2, 4) X(64, 3, 2, 1) X(64, 3, 2, 4) X(64, 4, 2, 1) X(64, 4, 2, 4)
+// k_step_csr instances (G, KCH, S), float4 lanes, chunks of kCsrNch rows
+#define PT_CSTEPS(X)                                                                 \
+    X(2, 1, 1) X(4, 1, 1) X(8, 1, 1) X(16, 1, 1) X(32, 1, 1) X(64, 1, 1)             \
+    X(2, 1, 2) X(4, 1, 2) X(8, 1, 2) X(16, 1, 2) X(32, 1, 2) X(64, 1, 2)             \
+    X(2, 1, 4) X(4, 1, 4) X(8, 1, 4) X(16, 1, 4) X(32, 1, 4) X(64, 1, 4)             \
+    X(64, 2, 1) X(64, 2, 2) X(64, 2, 4) X(64, 3, 1) X(64, 3, 4) X(64, 4, 1) X(64, 4, 4)
+// C2 (S = 4, 7 negatives per group): chunks of 2 rows, double-buffered, measured fastest
+static constexpr int kCsrNch = 2;
 
-// TransE on the counting-sort path with float4 rows takes k_step_csr (PT_STEP_OLD=1: the sub-group
-// kernel k_step_sampled); raw-buffer byte offsets must fit in 31 bits
+// TransE on the counting-sort path with float4 rows takes k_step_csr; raw-buffer byte offsets must fit
+// in 31 bits
 static bool csr_fast_path(const StepParams &P) {
-    static const bool old_step = [] {
-        const char *v = pt_tuning_env("PT_STEP_OLD");
-        return v && atoi(v) != 0;
-    }();
     const int64_t lim = int64_t(1) << 31;
     const bool fits31 = (P.ent_total + P.rel_total + P.batch_size * P.neg) * P.dim * 4 < lim;
-    return P.model == 0 && P.dim % 4 == 0 && fits31 && !old_step;
+    return P.model == 0 && P.dim % 4 == 0 && fits31;
 }
 
 // whether launch_step can take this (P, neg) on the in-kernel-sampled path: k_step_csr has no LDS
@@ -626,29 +623,26 @@ hipError_t launch_step(const StepParams &P, const DeviceGraph &g, const uint64_t
 #undef PT_STEP
         return hipErrorInvalidValue;
     }
-    // TransE on a counting-sort batch with float4 rows: k_step_csr (S lane groups per positive);
-    // PT_STEP_G / PT_STEP_S / PT_STEP_NCH override its shape
+    // TransE on a counting-sort batch with float4 rows: k_step_csr (S lane groups per positive)
     if (csr && csr_fast_path(P)) {
         const int64_t chunks = P.dim / 4;
         int G = 2;
         while (G < chunks && G < 64) G <<= 1;
-        if (const char *v = pt_tuning_env("PT_STEP_G")) G = atoi(v);
         const int KCH = (int)((chunks + G - 1) / G);
         // split a positive's negatives over S lane groups of one block (more waves in flight: the step
         // is latency-bound when one group walks all negatives)
         int S = 1;
         while (S < 4 && S * 2 <= 256 / G && P.neg >= 6 * S * 2) S *= 2;
-        if (const char *v = pt_tuning_env("PT_STEP_S")) S = atoi(v);
-        int nch = 2;   // C2 (S = 4, 7 negatives per group): chunks of 2 rows, double-buffered, measured fastest
-        if (const char *v = pt_tuning_env("PT_STEP_NCH")) nch = atoi(v);
-#define PT_CSTEP(G_, K_, N_, S_)                                                                       \
-        if (G == G_ && KCH == K_ && nch == N_ && S == S_) {                                          \
+#define PT_CSTEP(G_, K_, S_)                                                                           \
+        if (G == G_ && KCH == K_ && S == S_) {                                                       \
             constexpr int NT_ = S_ * G_ >= 256 || 256 % (S_ * G_) != 0 ? S_ * G_ : 256;             \
             const dim3 grid((unsigned)((P.batch_size * S_ * G_ + NT_ - 1) / NT_)), block(NT_);        \
             if (P.p_norm == 1)                                                                       \
-                hipLaunchKernelGGL((dev::k_step_csr<G_, 4, K_, N_, S_, 1, NT_>), grid, block, 0, st, P, sink, *csr); \
+                hipLaunchKernelGGL((dev::k_step_csr<G_, 4, K_, kCsrNch, S_, 1, NT_>), grid, block, 0, st, P, sink, \
+                                   *csr);                                                              \
             else                                                                                     \
-                hipLaunchKernelGGL((dev::k_step_csr<G_, 4, K_, N_, S_, 2, NT_>), grid, block, 0, st, P, sink, *csr); \
+                hipLaunchKernelGGL((dev::k_step_csr<G_, 4, K_, kCsrNch, S_, 2, NT_>), grid, block, 0, st, P, sink, \
+                                   *csr);                                                              \
             return hipGetLastError();                                                                \
         }
         PT_CSTEPS(PT_CSTEP)
@@ -658,15 +652,9 @@ hipError_t launch_step(const StepParams &P, const DeviceGraph &g, const uint64_t
     {
         const Shape s = pick_shape(P.dim, false);
         // split a positive's negatives over 4 lane groups when there are enough of them
-        // (PT_STEP_S = 1 | 2 | 4 and PT_STEP_NCH override, for tuning)
-        int S = (P.neg >= 8 && 256 / s.G >= 4) ? 4 : 1;
-        if (const char *v = pt_tuning_env("PT_STEP_S")) {
-            const int want = atoi(v);
-            if ((want == 1 || want == 2 || want == 4) && 256 / s.G >= want) S = want;
-        }
+        const int S = (P.neg >= 8 && 256 / s.G >= 4) ? 4 : 1;
         const int64_t nper = (P.neg + S - 1) / S;
         int nch = pick_nch(nper, s.KCH * s.VEC);
-        if (const char *v = pt_tuning_env("PT_STEP_NCH")) nch = atoi(v);
         const int64_t gpb = 256 / s.G, ppb = gpb / S;
         const dim3 grid((unsigned)((P.batch_size + ppb - 1) / ppb)), block(256);
         size_t lds = (size_t)ppb * (size_t)P.neg * sizeof(int64_t) * (csr ? 2 : 1);

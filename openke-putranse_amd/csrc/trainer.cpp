@@ -41,7 +41,8 @@ struct pt_trainer {
     int64_t lpart_cap = 0;                             // W.lpart capacity (positives)
     int device = -1;
     hipStream_t cap = nullptr;
-    // the split sampler's second launch of a chunk (sample_split_head): its stream and the fork / join events
+    // the split sampler's second launch of a chunk (enqueue_sample_split, pt_trainer_sample_csr only): its stream
+    // and the fork / join events
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int64_t split_override = -1;                        // pt_trainer_set_sample_split: head steps, 0 off, -1 auto
@@ -311,26 +312,10 @@ static int enqueue_sample_chunk(pt_trainer *t, pt_sampler *s, pt::CsrWork &w, in
     return PT_OK;
 }
 
-// Steps of a split-sampler chunk sampled ahead of the first step (0: the chunk is sampled by one launch). The
-// batch stream does not depend on the tables, so the chunk's other steps can be sampled by a second launch on
-// the trainer's side stream while the first steps train: the chunk's first step then waits for `head` steps'
-// sampling instead of the whole chunk's (the driver's 20-step chunk: 52 us). Opt-in (pt_trainer_set_sample_split;
-// the tuning build's PT_SAMPLE_SPLIT): measured slower on the driver's command, 38.4 -> 39.6 us per step at
-// head 1, 2 or 4 - the side launch's workgroups take the CUs of the steps it runs beside (step 0: 22 -> 43 us)
-// and the join across hardware queues leaves the main queue idle for ~11 us (profiles/r05_c2_split_sampling.json).
-// Not under the measurement hook (its events time each launch alone).
-static int64_t sample_split_head(const pt_trainer *t, int path, int64_t calls, const Timing *tm) {
-    if (path != PT_PATH_PART || tm) return 0;
-    int64_t h = t->split_override;
-    if (h < 0) {
-        h = 0;
-        if (const char *v = pt_tuning_env("PT_SAMPLE_SPLIT")) h = atoll(v);
-    }
-    return h > 0 && h < calls ? h : 0;
-}
-
 // A split-sampler chunk in two launches: the first `head` calls on `st`, the rest on the trainer's side stream
-// forked from `st` after it (neither launch advances the streams: join_sample_split does, after both).
+// forked from `st` after it (neither launch advances the streams: join_sample_split does, after both). What is
+// left of the two-launch split sampling, which training runs no longer use (measured slower):
+// pt_trainer_sample_csr alone takes it, after pt_trainer_set_sample_split.
 static int enqueue_sample_split(pt_trainer *t, pt_sampler *s, pt::CsrWork &w, int64_t bs, int64_t neg, int64_t bern,
                                 int64_t filter, int64_t calls, int64_t head, hipStream_t st) {
     const pt::DeviceGraph dg = s->g->dev;
@@ -373,17 +358,10 @@ static int enqueue_run(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, in
         const int64_t chunk = t->csr_chunk;
         for (int64_t c0 = 0; c0 < steps; c0 += chunk) {
             const int64_t calls = std::min(chunk, steps - c0);
-            const int path = choose_path(t, calls, bs, neg, sample_mode(t));
-            const int64_t head = sample_split_head(t, path, calls, tm);
-            // (either sets t->csr.rank_only, read by the steps and by pt_trainer_run_timed's re-timing)
-            int rc = head ? enqueue_sample_split(t, s, t->csr, bs, neg, bern, filter, calls, head, st)
-                          : enqueue_sample_chunk(t, s, t->csr, bs, neg, bern, filter, calls, sample_mode(t), st, tm);
+            // (sets t->csr.rank_only, read by the steps and by pt_trainer_run_timed's re-timing)
+            int rc = enqueue_sample_chunk(t, s, t->csr, bs, neg, bern, filter, calls, sample_mode(t), st, tm);
             if (rc) return rc;
             for (int64_t j = 0; j < calls; ++j) {
-                if (head && j == head) {   // the rest of the chunk sampled: join, then advance the streams
-                    rc = join_sample_split(t, s, bs, neg, calls, st);
-                    if (rc) return rc;
-                }
                 const pt::CsrWork v = pt::csr_view(t->csr, j, bs, neg);
                 float *loss = d_losses ? d_losses + c0 + j : nullptr;
                 PT_TIMED(2, pt::launch_step(P, dg, s->d_states, s->threads, (int)bern, (int)filter, nullptr, nullptr,
@@ -514,8 +492,7 @@ extern "C" int pt_trainer_set_sampling(pt_trainer *t, int32_t path, int64_t part
 extern "C" int pt_trainer_set_sample_split(pt_trainer *t, int64_t head) {
     PT_CHECK(t, PT_EINVAL, "null trainer");
     PT_CHECK(head >= -1, PT_EINVAL, "head must be >= -1");
-    t->split_override = head;
-    t->drop_graphs();   // captured epochs hold the previous choice
+    t->split_override = head;   // read by pt_trainer_sample_csr only: captured epochs do not depend on it
     return PT_OK;
 }
 

@@ -181,23 +181,25 @@ def test_split_sampler_two_launches(case, head):
         ctx.close()
 
 
-def test_split_sampling_run_equals_single_launch():
-    """pt_trainer_run over a 20-step chunk (the driver's shape) with the chunk's sampling split in two launches
-    (opt-in) and in one: the same per-step losses and tables, up to the float-atomic order of the step."""
+def test_part_path_run_equals_two_pass():
+    """pt_trainer_run over a 20-step chunk (the driver's shape) sampled by the default choice (k_sample_part: bucket
+    ranks that the step kernel resolves) and by the two-pass form (pt_trainer_set_sampling): the same per-step losses
+    and tables, up to the float-atomic order of the step."""
     from openke import _native
     L = _native.lib()
     res = []
-    for head in (0, 2):
+    for forced, path in ((False, "part"), (True, "twopass")):
         ctx = _Ctx(29, dim=24)
         try:
             g = torch.Generator().manual_seed(3)
             ctx.ent.copy_(((torch.rand(ctx.ent.shape, generator=g) - 0.5) * 0.2).cuda())
             ctx.rel.copy_(((torch.rand(ctx.rel.shape, generator=g) - 0.5) * 0.2).cuda())
-            _native.check(L.pt_trainer_set_sample_split(ctx.t, head))
+            if forced:
+                _native.check(L.pt_trainer_set_sampling(ctx.t, PATHS[path], 0))
             losses = torch.zeros(20, device="cuda")
             _native.check(L.pt_trainer_run(ctx.t, ctx.s, 100, 25, 1, 1, 20, _native.ptr(losses), _native.stream()))
             torch.cuda.synchronize()
-            assert L.pt_trainer_last_path(ctx.t) == PATHS["part"]
+            assert L.pt_trainer_last_path(ctx.t) == PATHS[path]
             res.append((losses.cpu(), ctx.ent.cpu(), ctx.rel.cpu()))
         finally:
             ctx.close()
