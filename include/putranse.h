@@ -78,13 +78,14 @@ int pt_sampler_sample_ex(pt_sampler *s, int64_t bs, int64_t neg, int64_t neg_rel
 
 /* ------------------------------------------------------------------ training ---------------- */
 enum { PT_TRANSE = 0, PT_TRANSH = 1 };
-enum { PT_SGD = 0, PT_ADAGRAD = 1 };
+enum { PT_SGD = 0, PT_ADAGRAD = 1, PT_ADAM = 2 };
 
 typedef struct {
     int32_t model;        /* PT_TRANSE | PT_TRANSH */
     int32_t p_norm;       /* 1 or 2  (TransE.py:46-60) */
     int32_t norm_flag;    /* F.normalize of h, r, t before scoring */
-    int32_t opt;          /* PT_SGD | PT_ADAGRAD (Trainer.py:62-88; eps 1e-10, lr_decay 0) */
+    int32_t opt;          /* PT_SGD | PT_ADAGRAD (Trainer.py:62-88; eps 1e-10, lr_decay 0) | PT_ADAM (state:
+                           * pt_trainer_set_adam) */
     float lr;
     float margin;         /* MarginLoss margin (MarginLoss.py:24-28) */
     int64_t ent_total, rel_total, dim;
@@ -128,6 +129,43 @@ int pt_trainer_set_sample_split(pt_trainer *t, int64_t head);
  * arrival order (float atomics) and is faster. on = 0 returns to the fast path. */
 int pt_trainer_set_deterministic(pt_trainer *t, int32_t on);
 int pt_trainer_get_deterministic(const pt_trainer *t);
+
+/* Loss of the external-batch step (batch_h != NULL). The default is plain MarginLoss on the raw distance, which is
+ * what every trainer computes until this is called. kind: PT_LOSS_MARGIN (MarginLoss.py:24-31; its margin is
+ * pt_model_desc.margin) or PT_LOSS_SIGMOID (SigmoidLoss.py:19-26). adv != 0: self-adversarial weights over a
+ * positive's negatives, softmax(-temperature * n) for the margin loss and softmax(temperature * n) for the sigmoid
+ * loss, constants of the backward pass (else 1 / neg). score_margin_flag != 0: the model carries its own margin
+ * (TransE.py:62-67) and the score handed to the loss is score_margin - d instead of the distance d.
+ * Anything but the default trains TransE only, on external batches only (PT_ENOTSUP from pt_trainer_step with
+ * batch_h == NULL, pt_trainer_run, pt_trainer_run_timed, the reference-order mode and TransH). */
+enum { PT_LOSS_MARGIN = 0, PT_LOSS_SIGMOID = 1 };
+typedef struct {
+    int32_t kind;               /* PT_LOSS_MARGIN | PT_LOSS_SIGMOID */
+    int32_t adv;                /* self-adversarial weights on / off */
+    float temperature;          /* adv_temperature */
+    int32_t score_margin_flag;  /* the model's margin_flag */
+    float score_margin;         /* the model's margin */
+} pt_loss_desc;
+int pt_trainer_set_loss(pt_trainer *t, const pt_loss_desc *loss);
+/* State of PT_ADAM (torch.optim.Adam as Trainer.py:77-82 builds it: no weight decay, no amsgrad): device arrays
+ * exp_avg / exp_avg_sq shaped like the tables (norm_* NULL for TransE), the betas, eps and the number of steps
+ * already done. Adam is dense: every step updates every row of every table (k_apply_adam). The trainer counts the
+ * steps from `step` on (pt_trainer_adam_step reads the count; -1 for a null trainer); the tables share the count.
+ * Adam trains external batches only (PT_ENOTSUP otherwise, as for pt_trainer_set_loss), TransE and TransH. */
+typedef struct {
+    float *ent_m, *rel_m, *norm_m;   /* exp_avg */
+    float *ent_v, *rel_v, *norm_v;   /* exp_avg_sq */
+    double beta1, beta2, eps;        /* doubles: 1 - beta is formed in double, as torch forms it */
+    int64_t step;
+} pt_adam_state;
+int pt_trainer_set_adam(pt_trainer *t, const pt_adam_state *state);
+int64_t pt_trainer_adam_step(const pt_trainer *t);
+/* Measurement hook of the external-batch step (tools/bench_adv.py): `steps` steps on ONE device batch (layout of
+ * pt_trainer_step), launched one by one with events around both launches of every step. ms2[0] = mean duration of
+ * the step kernel (k_step / k_step_adv), ms2[1] = of the apply kernel (k_apply / k_apply_adam). The steps train:
+ * tables, optimizer state and the Adam step count advance, *d_loss accumulates. Synchronizes the stream. */
+int pt_trainer_steps_timed(pt_trainer *t, int64_t bs, int64_t neg, const int64_t *d_batch_h, const int64_t *d_batch_t,
+                           const int64_t *d_batch_r, int64_t steps, float *d_loss, float *ms2, void *stream);
 
 /* Measurement hook: `steps` in-kernel-sampled steps launched one by one (no graph) with an event pair
  * around every launch on `stream`. ms4[k] = total duration of kernel kind k divided by `steps`:

@@ -1,0 +1,148 @@
+// HIP kernel of the dense Adam apply pass for gfx950: the counterpart of k_apply (apply.hip) for torch.optim.Adam
+// as Trainer.py:77-82 builds it (betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad).
+//
+// Adam is dense: every row of every table moves on every step (a row with a zero gradient still decays m and v and
+// moves while its m is nonzero), so one lane group (device.h row layout) owns one row of one table:
+//   flagged row:   load its gradient row, multiply by the normalise Jacobian of the pre-step row where the table's
+//                  gradient is in normalised space, re-zero the gradient row and the flag;
+//   unflagged row: g = 0 without reading the gradient row;
+//   every row:     m' = m + (1 - b1)(g - m);  v' = b2 v + (1 - b2) g^2;
+//                  w' = w - step_size * m' / (sqrt(v') / bc2_sqrt + eps)
+// with step_size = lr / (1 - b1^t) and bc2_sqrt = sqrt(1 - b2^t) computed on the host in double, and IEEE sqrt and
+// division (the denominator is the ill-conditioned part). Block 0 reduces the step's loss partials in a fixed order.
+// Floor: w, m, v read and written = 6 row-array passes over all tables (+ the touched gradient rows).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "device.h"
+#include "kernels.h"
+
+namespace pt {
+namespace dev {
+
+struct AdamTable {
+    float *w, *m, *v, *grad;
+    int *flag;
+    int64_t rows;
+    int jacobian;
+};
+struct AdamApply {
+    AdamTable t[3];
+    int ntab;
+    int64_t dim;
+    float beta2, omb1, omb2, eps, step_size, bc2_sqrt;   // omb = 1 - beta, formed on the host in double
+    // loss (block 0): loss (+)= scale * sum(lpart[0 .. bs)) + cst
+    float *loss;
+    const float *lpart;
+    int64_t bs;
+    float scale, cst;
+    int loss_assign;
+};
+
+__device__ __forceinline__ void adam_block0(const AdamApply &A) {
+    const int lane = (int)threadIdx.x;
+    float s = 0.f;
+    for (int64_t i0 = lane; i0 < A.bs; i0 += 64 * 8) {   // 8 independent loads in flight per lane
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = i0 + u * 64 < A.bs ? A.lpart[i0 + u * 64] : 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += v[u];
+    }
+    s = gsum<64>(s);
+    if (lane == 0) {
+        const float l = s * A.scale + A.cst;
+        if (A.loss_assign) *A.loss = l; else *A.loss += l;
+    }
+}
+
+template <int G, int VEC, int KCH>
+__global__ __launch_bounds__(256) void k_apply_adam(AdamApply A) {
+    using Vec = V<G, VEC, KCH>;
+    constexpr int GPB = 256 / G;
+    const int lane = threadIdx.x % G;
+    int64_t row = (int64_t)blockIdx.x * GPB + threadIdx.x / G;
+    if (blockIdx.x == 0 && threadIdx.x < 64 && A.loss && A.lpart) adam_block0(A);
+    int ti = 0;
+    while (ti < A.ntab && row >= A.t[ti].rows) {
+        row -= A.t[ti].rows;
+        ++ti;
+    }
+    if (ti >= A.ntab) return;
+    const AdamTable &T = A.t[ti];
+    const int D = (int)A.dim;
+    const int64_t off = row * D;
+    Vec x, m, v, g;
+    vload(x, T.w + off, D, lane);
+    vload(m, T.m + off, D, lane);
+    vload(v, T.v + off, D, lane);
+    const int flagged = T.flag[row];
+    if (flagged) {
+        Vec gr;
+        vload(gr, T.grad + off, D, lane);
+        if (T.jacobian) {
+            const float n = sqrtf(vdot(x, x));
+            vnormalize_bwd(x, n, gr, g);
+        } else {
+            g = gr;
+        }
+        Vec z;
+        vzero(z);
+        vstore(z, T.grad + off, D, lane);
+        if (lane == 0) T.flag[row] = 0;
+    } else {
+        vzero(g);
+    }
+#pragma unroll
+    for (int i = 0; i < Vec::N; ++i) {
+        m.x[i] = m.x[i] + A.omb1 * (g.x[i] - m.x[i]);
+        v.x[i] = A.beta2 * v.x[i] + A.omb2 * g.x[i] * g.x[i];
+        const float den = sqrtf(v.x[i]) / A.bc2_sqrt + A.eps;
+        x.x[i] = x.x[i] - A.step_size * (m.x[i] / den);
+    }
+    vstore(m, T.m + off, D, lane);
+    vstore(v, T.v + off, D, lane);
+    vstore(x, T.w + off, D, lane);
+}
+
+}  // namespace dev
+
+hipError_t launch_apply_adam(const StepParams &P, const StepWorkspace &W, const AdamParams &Ad, int64_t bs,
+                             float loss_scale, float loss_cst, float *loss, hipStream_t st) {
+    const Shape s = pick_shape(P.dim);
+    dev::AdamApply A{};
+    A.ntab = 0;
+    const int ent_j = P.model == 0 && P.norm_flag;   // (gradient conventions per table: device.h group_step)
+    A.t[A.ntab++] = dev::AdamTable{P.ent, Ad.m[0], Ad.v[0], W.gent, W.fent, P.ent_total, ent_j};
+    A.t[A.ntab++] = dev::AdamTable{P.rel, Ad.m[1], Ad.v[1], W.grel, W.frel, P.rel_total, P.norm_flag};
+    if (P.model == 1) A.t[A.ntab++] = dev::AdamTable{P.normv, Ad.m[2], Ad.v[2], W.gnorm, W.fnorm, P.rel_total, 1};
+    for (int i = 0; i < A.ntab; ++i)
+        if (!A.t[i].m || !A.t[i].v) return hipErrorInvalidValue;
+    A.dim = P.dim;
+    A.beta2 = (float)Ad.beta2;
+    A.omb1 = (float)(1.0 - Ad.beta1);
+    A.omb2 = (float)(1.0 - Ad.beta2);
+    A.eps = (float)Ad.eps;
+    A.step_size = Ad.step_size; A.bc2_sqrt = Ad.bc2_sqrt;
+    A.loss = loss;
+    A.lpart = W.lpart;
+    A.bs = bs;
+    A.scale = loss_scale;
+    A.cst = loss_cst;
+    A.loss_assign = P.loss_assign;
+    int64_t rows = 0;
+    for (int i = 0; i < A.ntab; ++i) rows += A.t[i].rows;
+    const int64_t gpb = 256 / s.G;
+    const dim3 grid((unsigned)((rows + gpb - 1) / gpb)), block(256);
+#define PT_ADAM_K(G_, V_, K_)                                                          \
+    if (s.G == G_ && s.VEC == V_ && s.KCH == K_) {                                    \
+        hipLaunchKernelGGL((dev::k_apply_adam<G_, V_, K_>), grid, block, 0, st, A);   \
+        return hipGetLastError();                                                     \
+    }
+    PT_SHAPES(PT_ADAM_K)
+#undef PT_ADAM_K
+    return hipErrorInvalidValue;
+}
+
+}  // namespace pt

@@ -43,11 +43,12 @@ int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
     PT_CHECK(m, PT_EINVAL, "null model descriptor");
     PT_CHECK(m->model == PT_TRANSE || m->model == PT_TRANSH, PT_EINVAL, "model must be PT_TRANSE or PT_TRANSH");
     PT_CHECK(m->p_norm == 1 || m->p_norm == 2, PT_ENOTSUP, "p_norm must be 1 or 2");
-    PT_CHECK(m->opt == PT_SGD || m->opt == PT_ADAGRAD, PT_EINVAL, "opt must be PT_SGD or PT_ADAGRAD");
+    PT_CHECK(m->opt == PT_SGD || m->opt == PT_ADAGRAD || m->opt == PT_ADAM, PT_EINVAL,
+             "opt must be PT_SGD, PT_ADAGRAD or PT_ADAM");
     PT_CHECK(pt::shape_supported(m->dim), PT_ENOTSUP, "embedding dim " + std::to_string(m->dim) + " not supported");
     PT_CHECK(m->ent && m->rel && m->ent_total > 0 && m->rel_total > 0, PT_EINVAL, "missing tables");
     PT_CHECK(m->model == PT_TRANSE || m->normv, PT_EINVAL, "TransH needs norm_vector");
-    PT_CHECK(m->opt == PT_SGD || (m->ent_acc && m->rel_acc && (m->model == PT_TRANSE || m->norm_acc)), PT_EINVAL,
+    PT_CHECK(m->opt != PT_ADAGRAD || (m->ent_acc && m->rel_acc && (m->model == PT_TRANSE || m->norm_acc)), PT_EINVAL,
              "Adagrad needs state_sum buffers");
     P.model = m->model;
     P.p_norm = m->p_norm;

@@ -128,6 +128,36 @@ hipError_t launch_step(const StepParams &P, const DeviceGraph &g, const uint64_t
                        float *loss, hipStream_t st, const CsrWork *csr = nullptr);
 hipError_t launch_apply(const StepParams &P, const StepWorkspace &W, uint64_t *states, int64_t threads, int64_t bs,
                         int64_t dpp, float *loss, hipStream_t st, const CsrWork *csr = nullptr);
+// Loss of the weighted external-batch step (step_adv.hip; pt_loss_desc): kind 0 MarginLoss (margin = StepParams::
+// margin), 1 SigmoidLoss; adv = self-adversarial weights softmax(+-temp * n) over a positive's negatives (else 1/K);
+// mflag = the model's own margin: the score handed to the loss is gamma - d instead of d
+struct LossParams {
+    int kind = 0, adv = 0;
+    float temp = 0.f;
+    int mflag = 0;
+    float gamma = 0.f;
+    bool plain() const { return kind == 0 && !adv && !mflag; }
+};
+// lpart[b] of k_step_adv sums to the step's loss as scale * sum + cst
+inline void loss_affine(const LossParams &L, const StepParams &P, float *scale, float *cst) {
+    *scale = L.kind == 1 ? -0.5f / (float)P.batch_size : 1.0f / (float)P.batch_size;
+    *cst = L.kind == 1 ? 0.f : P.margin;
+}
+// dense Adam (adam.hip; pt_adam_state): m / v per table, the step's bias corrections computed on the host in double
+struct AdamParams {
+    float *m[3] = {nullptr, nullptr, nullptr}, *v[3] = {nullptr, nullptr, nullptr};
+    double beta1 = 0.9, beta2 = 0.999, eps = 1e-8;   // (1 - beta in double: 1.0f - 0.999f is 1.3e-5 off 0.001)
+    float step_size = 0.f;   // lr / (1 - beta1^t)
+    float bc2_sqrt = 1.f;    // sqrt(1 - beta2^t)
+};
+// largest neg k_step_adv takes at this dim (a lane group's scores and its transpose row sit in LDS)
+int64_t step_adv_max_neg(int64_t dim);
+hipError_t launch_step_adv(const StepParams &P, const LossParams &L, const int64_t *bh, const int64_t *bt,
+                           const int64_t *br, const StepWorkspace &W, hipStream_t st);
+// every row of every table: gradient row (flagged rows only) -> normalize Jacobian -> Adam; block 0 reduces the
+// loss partials: loss (+)= loss_scale * sum(lpart) + loss_cst
+hipError_t launch_apply_adam(const StepParams &P, const StepWorkspace &W, const AdamParams &A, int64_t bs,
+                             float loss_scale, float loss_cst, float *loss, hipStream_t st);
 hipError_t launch_score(const StepParams &P, int mode, const int64_t *h, const int64_t *t, const int64_t *r, int64_t n,
                         float *out, hipStream_t st);
 hipError_t launch_score_queries(const StepParams &P, int side, const int64_t *qh, const int64_t *qt, const int64_t *qr,

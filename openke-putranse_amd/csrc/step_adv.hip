@@ -1,0 +1,363 @@
+// HIP kernel of the weighted external-batch step for gfx950: TransE under SigmoidLoss (with or without the
+// self-adversarial weights), MarginLoss with the self-adversarial weights, and plain MarginLoss on a model that
+// carries its own margin (score = gamma - d).
+//
+// Semantics: d = ||h^ + r^ - t^||_p (TransE.py:46-60, rows normalised under norm_flag), score s = gamma - d with the
+// model's margin (TransE.py:62-67) else d; a batch of B positives with K negatives each in the reference layout
+// (NegativeSampling.py:13-21: negative k of positive i at (k + 1) * B + i);
+//   SigmoidLoss.py:19-26:  L = -1/2 [mean_i logsig(p_i) + mean_i sum_k w_ik logsig(-n_ik)],  w = softmax_k(T n) | 1/K
+//   MarginLoss.py:24-31:   L = mean_i sum_k w_ik max(p_i - n_ik, -m) + m,                    w = softmax_k(-T n) | 1/K
+// with the weights detached (constants of the backward pass) and torch's maximum tie -> half.
+//
+// Mapping: the lane-group row layout of device.h; ONE lane group owns a positive and all its negatives (the softmax
+// couples them) and walks them twice. Pass 1 forms v_k and stores d_k in LDS (K floats per group); the group then
+// finds the extreme score, the softmax and the loss partial lane-parallel over those K floats and overwrites d_k by
+// dL/dd_k; pass 2 re-forms v_k (same instructions: the same bits) and emits gradients: entity and relation
+// gradients in normalised space (the apply pass multiplies by the normalise Jacobian), the positive's relation and
+// uncorrupted side summed in registers (chunk partials first), every other row through float atomics into the
+// trainer's gradient rows plus touched flags (row_atomic below). A negative that shares the positive's relation and
+// one entity (every cross-sampled negative, and every normal-mode entity corruption) costs one row load per pass:
+// h^ + r^ and t^ stay in registers. Rows of NCH negatives are in flight together. Pass 2 re-reads the rows it needs
+// (K x dim x 4 bytes per positive: L2-sized). STAGE = true (measurement build only, PT_ADV_STAGE=1) is the alternative
+// that was measured against it: pass 1 keeps the raw rows of a group's negatives in LDS and pass 2 reads them there
+// (K x dim x 4 bytes of LDS per positive: one positive per CU at K = 64, dim = 512). It is slower (DESIGN.md
+// section 4), so the product build does not instantiate it.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+
+#include "tuning.h"
+#include "device.h"
+#include "kernels.h"
+
+namespace pt {
+namespace dev {
+
+template <int G>
+__device__ __forceinline__ float gmax(float v) {
+#pragma unroll
+    for (int o = 1; o < G; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// overflow-safe log(sigmoid(x)) and sigmoid(x)
+__device__ __forceinline__ float logsig(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
+__device__ __forceinline__ float sigm(float x) {
+    const float e = expf(-fabsf(x));
+    return (x >= 0.f ? 1.0f : e) / (1.0f + e);
+}
+
+// Float atomics of a row vector into a gradient row. float4 lanes would make one atomic wave-instruction touch
+// floats 16 B apart (4x the cache lines): the vector passes through the group's LDS row `tb` instead, so lane l adds
+// floats l, l + G, ... (256 contiguous bytes per instruction at G = 64), as k_step_csr does for the positive's rows
+// (measured here: DESIGN.md section 4). The group is inside one wave, whose LDS accesses execute in program order.
+template <int G, int VEC, int KCH>
+__device__ __forceinline__ void row_atomic(const V<G, VEC, KCH> &g, float *__restrict__ row, float *tb, int D,
+                                           int lane) {
+    if constexpr (VEC == 1) {
+        vatomic(g, row, D, lane);
+    } else {
+#pragma unroll
+        for (int k = 0; k < KCH; ++k) {
+            const int c = k * G + lane;
+            *reinterpret_cast<float4 *>(tb + c * 4) =
+                make_float4(g.x[k * 4 + 0], g.x[k * 4 + 1], g.x[k * 4 + 2], g.x[k * 4 + 3]);
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int j = 0; j < KCH * VEC; ++j) {
+            const int c = j * G + lane;
+            if (c < D) atomicAdd(row + c, tb[c]);
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+struct AdvSink {
+    float *gent, *grel;
+    int *fent, *frel;
+    template <int G, int VEC, int KCH>
+    __device__ __forceinline__ void ent(int64_t row, const V<G, VEC, KCH> &g, float *tb, int D, int lane) const {
+        row_atomic(g, gent + row * D, tb, D, lane);
+        if (lane == 0) fent[row] = 1;
+    }
+    template <int G, int VEC, int KCH>
+    __device__ __forceinline__ void rel(int64_t row, const V<G, VEC, KCH> &g, float *tb, int D, int lane) const {
+        row_atomic(g, grel + row * D, tb, D, lane);
+        if (lane == 0) frel[row] = 1;
+    }
+};
+
+template <int G, int VEC, int KCH, int NCH, bool STAGE = false>
+__global__ __launch_bounds__(256) void k_step_adv(StepParams P, LossParams L, const int64_t *__restrict__ bh,
+                                                  const int64_t *__restrict__ bt, const int64_t *__restrict__ br,
+                                                  AdvSink sink, float *__restrict__ lpart) {
+    using Vec = V<G, VEC, KCH>;
+    static_assert(!STAGE || VEC == 4, "the staged variant exists for float4 rows");
+    constexpr int RW = VEC == 4 ? KCH * G * VEC : 0;   // floats of a group's transpose row (row_atomic)
+    // [groups per block][RW] transpose rows, then [groups per block][neg] scores (STAGE: then [groups per block]
+    // [neg][RW] staged rows, each lane writing and reading its own float4 chunks)
+    extern __shared__ __attribute__((aligned(16))) float s_lds[];
+    const int gpb = (int)blockDim.x / G;
+    const int lane = threadIdx.x % G;
+    const int grp = threadIdx.x / G;
+    const int64_t bs = P.batch_size;
+    const int neg = (int)P.neg;
+    const int64_t b = (int64_t)blockIdx.x * gpb + grp;
+    if (b >= bs) return;   // (no block-wide barrier below: a group is inside one wave)
+    float *tb = s_lds + (size_t)grp * RW;
+    float *sc = s_lds + (size_t)gpb * RW + (size_t)grp * neg;
+    float *stage = s_lds + (size_t)gpb * (RW + neg) + (size_t)grp * neg * RW;
+    const int D = (int)P.dim;
+    const int p = P.p_norm;
+    const bool nf = P.norm_flag != 0;
+    // ---- positive
+    const int64_t hp = bh[b], tp = bt[b], rp = br[b];
+    Vec hh, th, rh, base, vpos;
+    {
+        Vec H, T, R;
+        vload(H, P.ent + hp * D, D, lane);
+        vload(T, P.ent + tp * D, D, lane);
+        vload(R, P.rel + rp * D, D, lane);
+        if (nf) {
+            vnormalize(H, hh);
+            vnormalize(R, rh);
+            vnormalize(T, th);
+        } else {
+            hh = H; rh = R; th = T;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < Vec::N; ++i) {
+        base.x[i] = hh.x[i] + rh.x[i];
+        vpos.x[i] = base.x[i] - th.x[i];
+    }
+    const float dp = vpnorm(vpos, p);
+    const float sg = L.mflag ? -1.f : 1.f;   // ds / dd
+    const float ps = L.mflag ? L.gamma - dp : dp;
+    float dldp = 0.f;                        // dL / d(positive score)
+    // on-chip sums over the negatives that share the positive's rows: aH = sum of dL/dv_k over those that keep its
+    // head (dL/dh^), aT = minus the sum over those that keep its tail (dL/dt^); dL/dr^ = aH - aT. Each chunk sums
+    // into accumulators of its own first (a K-term sequential float32 sum into one accumulator was measured
+    // 3e-7 off at K = 256; chunk partials bring it to 5e-8)
+    Vec aH, aT;
+    vzero(aH); vzero(aT);
+
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int c0 = 0; c0 < neg; c0 += NCH) {
+            int64_t hk[NCH], tk[NCH], rk[NCH];
+            int kind[NCH];   // 0: shares (h, r): row t_k; 1: shares (r, t): row h_k; 2: any other slot; -1: nothing to do
+            Vec E[NCH], cH, cT;
+            vzero(cH); vzero(cT);
+#pragma unroll
+            for (int u = 0; u < NCH; ++u) {
+                kind[u] = -1;
+                if (c0 + u >= neg) continue;
+                if (pass == 1 && sc[c0 + u] == 0.f) continue;   // no gradient through this negative
+                const int64_t o = (int64_t)(c0 + u + 1) * bs + b;
+                hk[u] = bh[o]; tk[u] = bt[o]; rk[u] = br[o];
+                kind[u] = rk[u] != rp ? 2 : (hk[u] == hp ? 0 : (tk[u] == tp ? 1 : 2));
+                if (kind[u] < 2 && !(STAGE && pass == 1))
+                    vload(E[u], P.ent + (kind[u] == 0 ? tk[u] : hk[u]) * D, D, lane);
+            }
+#pragma unroll
+            for (int u = 0; u < NCH; ++u) {
+                if (kind[u] < 0) continue;
+                Vec vk;
+                if (kind[u] < 2) {
+                    if constexpr (STAGE) {
+                        float4 *sr = reinterpret_cast<float4 *>(stage + (size_t)(c0 + u) * RW);
+#pragma unroll
+                        for (int k = 0; k < KCH; ++k) {
+                            if (pass == 0) {
+                                sr[k * G + lane] = make_float4(E[u].x[k * 4 + 0], E[u].x[k * 4 + 1],
+                                                               E[u].x[k * 4 + 2], E[u].x[k * 4 + 3]);
+                            } else {
+                                const float4 f = sr[k * G + lane];
+                                E[u].x[k * 4 + 0] = f.x; E[u].x[k * 4 + 1] = f.y;
+                                E[u].x[k * 4 + 2] = f.z; E[u].x[k * 4 + 3] = f.w;
+                            }
+                        }
+                    }
+                    Vec eh;
+                    if (nf) vnormalize(E[u], eh); else eh = E[u];
+                    if (kind[u] == 0) {
+#pragma unroll
+                        for (int i = 0; i < Vec::N; ++i) vk.x[i] = base.x[i] - eh.x[i];
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < Vec::N; ++i) vk.x[i] = (eh.x[i] + rh.x[i]) - th.x[i];
+                    }
+                } else {
+                    Vec A, B, C, a, bb, c;
+                    vload(A, P.ent + hk[u] * D, D, lane);
+                    vload(B, P.rel + rk[u] * D, D, lane);
+                    vload(C, P.ent + tk[u] * D, D, lane);
+                    if (nf) {
+                        vnormalize(A, a);
+                        vnormalize(B, bb);
+                        vnormalize(C, c);
+                    } else {
+                        a = A; bb = B; c = C;
+                    }
+#pragma unroll
+                    for (int i = 0; i < Vec::N; ++i) vk.x[i] = (a.x[i] + bb.x[i]) - c.x[i];
+                }
+                if (pass == 0) {
+                    const float d = vpnorm(vk, p);
+                    if (lane == 0) sc[c0 + u] = d;
+                    continue;
+                }
+                const float cd = sc[c0 + u];   // dL / dd_k
+                const float nd = p == 2 ? vpnorm(vk, 2) : 0.f;
+                Vec g, gn;   // dL/dv_k and its negation
+                vpnorm_bwd(vk, nd, p, cd, g);
+#pragma unroll
+                for (int i = 0; i < Vec::N; ++i) gn.x[i] = -g.x[i];
+                if (kind[u] == 0) {
+#pragma unroll
+                    for (int i = 0; i < Vec::N; ++i) cH.x[i] += g.x[i];
+                    sink.ent(tk[u], gn, tb, D, lane);
+                } else if (kind[u] == 1) {
+#pragma unroll
+                    for (int i = 0; i < Vec::N; ++i) cT.x[i] -= g.x[i];
+                    sink.ent(hk[u], g, tb, D, lane);
+                } else {
+                    sink.ent(hk[u], g, tb, D, lane);
+                    sink.rel(rk[u], g, tb, D, lane);
+                    sink.ent(tk[u], gn, tb, D, lane);
+                }
+            }
+            if (pass == 1) {
+#pragma unroll
+                for (int i = 0; i < Vec::N; ++i) {
+                    aH.x[i] += cH.x[i];
+                    aT.x[i] += cT.x[i];
+                }
+            }
+        }
+        if (pass == 1) break;
+        // ---- between the passes: weights, loss partial and dL/dd_k, lane-parallel over the group's scores
+        __builtin_amdgcn_wave_barrier();   // LDS order inside a wave is program order
+        const float invB = 1.0f / (float)bs;
+        float zt = 0.f, ext = 0.f, winv = 1.0f / (float)neg;
+        if (L.adv) {
+            zt = L.kind == 1 ? L.temp : -L.temp;
+            float mx = -INFINITY;
+            for (int k = lane; k < neg; k += G) {
+                const float n = L.mflag ? L.gamma - sc[k] : sc[k];
+                mx = fmaxf(mx, zt > 0.f ? n : -n);
+            }
+            mx = gmax<G>(mx);
+            ext = zt > 0.f ? mx : -mx;   // the score of the largest weight: every exponent below is <= 0
+            float se = 0.f;
+            for (int k = lane; k < neg; k += G) {
+                const float n = L.mflag ? L.gamma - sc[k] : sc[k];
+                se += expf(zt * (n - ext));
+            }
+            winv = 1.0f / gsum<G>(se);
+        }
+        float lp = 0.f, cs = 0.f;
+        for (int k = lane; k < neg; k += G) {
+            const float n = L.mflag ? L.gamma - sc[k] : sc[k];
+            const float w = L.adv ? expf(zt * (n - ext)) * winv : winv;
+            float c;   // dL / dn_k
+            if (L.kind == 1) {
+                lp += w * logsig(-n);
+                c = w * sigm(n) * (0.5f * invB);
+            } else {
+                const float a = ps - n, m = P.margin;
+                lp += w * (a > -m ? a : -m);
+                const float hc = a > -m ? 1.0f : (a == -m ? 0.5f : 0.f);
+                cs += w * hc;
+                c = -(w * hc) * invB;
+            }
+            sc[k] = c * sg;
+        }
+        lp = gsum<G>(lp);
+        if (L.kind == 1) {
+            lp += logsig(ps);
+            dldp = -sigm(-ps) * (0.5f * invB);
+        } else {
+            dldp = gsum<G>(cs) * invB;
+        }
+        if (lane == 0 && lpart) lpart[b] = lp;
+        __builtin_amdgcn_wave_barrier();
+    }
+    // ---- positive backward and the on-chip sums
+    Vec aR;
+#pragma unroll
+    for (int i = 0; i < Vec::N; ++i) aR.x[i] = aH.x[i] - aT.x[i];
+    if (dldp != 0.f) {
+        Vec g;
+        vpnorm_bwd(vpos, dp, p, dldp * sg, g);
+#pragma unroll
+        for (int i = 0; i < Vec::N; ++i) {
+            aH.x[i] += g.x[i];
+            aR.x[i] += g.x[i];
+            aT.x[i] -= g.x[i];
+        }
+    }
+    if (vnonzero(aR)) sink.rel(rp, aR, tb, D, lane);
+    if (vnonzero(aH)) sink.ent(hp, aH, tb, D, lane);
+    if (vnonzero(aT)) sink.ent(tp, aT, tb, D, lane);
+}
+
+}  // namespace dev
+
+// a group's K scores and its transpose row sit in LDS: at most 64 KB of it (the launch default) for one group
+static constexpr int64_t kAdvLdsFloats = 64 * 1024 / 4;
+static int64_t adv_row_floats(const Shape &s) { return s.VEC == 4 ? (int64_t)s.KCH * s.G * s.VEC : 0; }
+int64_t step_adv_max_neg(int64_t dim) { return kAdvLdsFloats - adv_row_floats(pick_shape(dim)); }
+
+hipError_t launch_step_adv(const StepParams &P, const LossParams &L, const int64_t *bh, const int64_t *bt,
+                           const int64_t *br, const StepWorkspace &W, hipStream_t st) {
+    if (P.batch_size <= 0) return hipSuccess;
+    if (P.model != 0 || P.neg < 1 || P.neg > step_adv_max_neg(P.dim)) return hipErrorInvalidValue;   // (cap >= 1 below)
+    const Shape s = pick_shape(P.dim);
+    // lane groups per block: 256 threads' worth, fewer when their score rows would not fit 64 KB of LDS (the block
+    // is then gpb * G threads, not always a multiple of 64: harmless, a group never straddles a wave and the kernel
+    // has no block-wide barrier)
+    int64_t gpb = 256 / s.G;
+    const int64_t rw = adv_row_floats(s);
+    const int64_t cap = kAdvLdsFloats / (P.neg + rw);
+    if (gpb > cap) gpb = cap;
+    dev::AdvSink sink{W.gent, W.grel, W.fent, W.frel};
+#ifdef PT_TUNING
+    // PT_ADV_STAGE=1: the LDS-staged pass 2 (float4 rows), as many groups per block as 160 KB of LDS hold
+    if (const char *v = pt_tuning_env("PT_ADV_STAGE")) {
+        const int64_t per = P.neg + rw + P.neg * rw, lim = 160 * 1024 / 4;
+        if (atoi(v) != 0 && s.VEC == 4 && per <= lim && P.neg % 4 == 0) {   // (float4-aligned staged rows)
+            const int64_t g2 = std::min<int64_t>(256 / s.G, lim / per);
+            const dim3 grid2((unsigned)((P.batch_size + g2 - 1) / g2)), block2((unsigned)(g2 * s.G));
+            const size_t lds2 = sizeof(float) * (size_t)(g2 * per);
+#define PT_ADVS(G_, V_, K_)                                                                                     \
+            if (s.G == G_ && s.KCH == K_) {                                                                    \
+                auto kern = dev::k_step_adv<G_, 4, K_, 4, true>;                                               \
+                hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                                   (int)lds2);                                                 \
+                if (e != hipSuccess) return e;                                                                 \
+                hipLaunchKernelGGL(kern, grid2, block2, lds2, st, P, L, bh, bt, br, sink, W.lpart);            \
+                return hipGetLastError();                                                                      \
+            }
+            PT_ADVS(2, 4, 1) PT_ADVS(4, 4, 1) PT_ADVS(8, 4, 1) PT_ADVS(16, 4, 1) PT_ADVS(32, 4, 1) PT_ADVS(64, 4, 1)
+            PT_ADVS(64, 4, 2)
+#undef PT_ADVS
+        }
+    }
+#endif
+    const dim3 grid((unsigned)((P.batch_size + gpb - 1) / gpb)), block((unsigned)(gpb * s.G));
+    const size_t lds = sizeof(float) * (size_t)(gpb * (P.neg + rw));
+#define PT_ADV(G_, V_, K_)                                                                                      \
+    if (s.G == G_ && s.VEC == V_ && s.KCH == K_) {                                                             \
+        hipLaunchKernelGGL((dev::k_step_adv<G_, V_, K_, 4>), grid, block, lds, st, P, L, bh, bt, br, sink,    \
+                           W.lpart);                                                                           \
+        return hipGetLastError();                                                                              \
+    }
+    PT_SHAPES(PT_ADV)
+#undef PT_ADV
+    return hipErrorInvalidValue;
+}
+
+}  // namespace pt

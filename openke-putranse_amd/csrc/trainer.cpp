@@ -2,10 +2,12 @@
 // counting-sort workspaces, the choice of sampling path per chunk, the launch sequence of a run (captured into
 // one hipGraph per epoch shape by pt_trainer_run), the measurement hook and the reference-order mode.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
+#include <string>
 #include <tuple>
 #include <vector>
 
@@ -57,6 +59,13 @@ struct pt_trainer {
     int64_t *ord_h = nullptr, *ord_t = nullptr, *ord_r = nullptr;
     float *ord_y = nullptr, *ord_score = nullptr, *ord_ds = nullptr;
     float *ord_g = nullptr;   // [4][seq][dim] per-slot gradient rows
+    // weighted losses and dense Adam (external batches only): pt_trainer_set_loss / pt_trainer_set_adam
+    pt::LossParams loss{};
+    pt::AdamParams adam{};
+    bool adam_set = false;
+    int64_t adam_step = 0;   // steps done
+    // anything the in-kernel-sampled, captured and reference-order paths do not compute
+    bool extended() const { return !loss.plain() || P.opt == PT_ADAM; }
     void drop_graphs() {
         for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
         graphs.clear();
@@ -381,16 +390,50 @@ static int enqueue_run(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, in
     return PT_OK;
 }
 
+// One step on an external batch: plain MarginLoss without a model margin -> k_step, any other loss -> k_step_adv;
+// SGD / Adagrad -> k_apply, Adam -> k_apply_adam (its step count advances here)
+// (ev: optional three events recorded before the step kernel, between the two kernels and after the apply kernel)
 static int enqueue_external(pt_trainer *t, int64_t bs, int64_t neg, const int64_t *bh, const int64_t *bt,
-                            const int64_t *br, float *d_loss, hipStream_t st) {
+                            const int64_t *br, float *d_loss, hipStream_t st, hipEvent_t *ev = nullptr) {
     pt::StepParams P = t->P;
     P.batch_size = bs;
     P.neg = neg;
     P.inv_count = 1.0f / (float)(bs * neg);
-    PT_HIP(pt::launch_step(P, pt::DeviceGraph{}, nullptr, 0, 0, 0, bh, bt, br, t->W, d_loss, st));
-    PT_HIP(pt::launch_apply(P, t->W, nullptr, 0, bs, 1 + 2 * neg, d_loss, st));
+    const bool adam = P.opt == PT_ADAM;
+    PT_CHECK(!adam || t->adam_set, PT_ESTATE, "PT_ADAM needs pt_trainer_set_adam before the first step");
+    float scale = P.inv_count, cst = P.margin;   // loss = scale * sum(lpart) + cst
+    if (ev) PT_HIP(hipEventRecord(ev[0], st));
+    if (t->loss.plain()) {
+        PT_HIP(pt::launch_step(P, pt::DeviceGraph{}, nullptr, 0, 0, 0, bh, bt, br, t->W, d_loss, st));
+    } else {
+        PT_CHECK(P.model == PT_TRANSE, PT_ENOTSUP,
+                 "SigmoidLoss, adversarial weights and a model margin train TransE only (TransH is not implemented)");
+        PT_CHECK(neg <= pt::step_adv_max_neg(P.dim), PT_ENOTSUP,
+                 "neg_ent " + std::to_string(neg) + " too large for the weighted step's LDS score buffer (max " +
+                     std::to_string(pt::step_adv_max_neg(P.dim)) + ")");
+        pt::loss_affine(t->loss, P, &scale, &cst);
+        PT_HIP(pt::launch_step_adv(P, t->loss, bh, bt, br, t->W, st));
+    }
+    if (ev) PT_HIP(hipEventRecord(ev[1], st));
+    if (adam) {
+        pt::AdamParams A = t->adam;
+        const double step = (double)(t->adam_step + 1);
+        A.step_size = (float)((double)P.lr / (1.0 - std::pow(A.beta1, step)));
+        A.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(A.beta2, step));
+        PT_HIP(pt::launch_apply_adam(P, t->W, A, bs, scale, cst, d_loss, st));
+        ++t->adam_step;
+    } else {
+        P.inv_count = scale;   // (the apply pass reads these two for the loss only)
+        P.margin = cst;
+        PT_HIP(pt::launch_apply(P, t->W, nullptr, 0, bs, 1 + 2 * neg, d_loss, st));
+    }
+    if (ev) PT_HIP(hipEventRecord(ev[2], st));
     return PT_OK;
 }
+
+static const char *kExtendedMsg =
+    "a non-default loss (pt_trainer_set_loss) and PT_ADAM train external batches only: in-kernel sampling, captured "
+    "runs and the reference-order mode are not implemented for them";
 
 // per-positive loss partials for batches of up to `bs` positives (grown on demand, never during a
 // capture: callers prepare before enqueueing)
@@ -504,6 +547,37 @@ extern "C" int pt_trainer_set_deterministic(pt_trainer *t, int32_t on) {
 }
 extern "C" int pt_trainer_get_deterministic(const pt_trainer *t) { return t && t->ordered ? 1 : 0; }
 
+extern "C" int pt_trainer_set_loss(pt_trainer *t, const pt_loss_desc *l) {
+    PT_CHECK(t && l, PT_EINVAL, "pt_trainer_set_loss: null argument");
+    PT_CHECK(l->kind == PT_LOSS_MARGIN || l->kind == PT_LOSS_SIGMOID, PT_EINVAL,
+             "loss kind must be PT_LOSS_MARGIN or PT_LOSS_SIGMOID");
+    pt::LossParams L{};
+    L.kind = l->kind;
+    L.adv = l->adv ? 1 : 0;
+    L.temp = l->adv ? l->temperature : 0.f;
+    L.mflag = l->score_margin_flag ? 1 : 0;
+    L.gamma = l->score_margin_flag ? l->score_margin : 0.f;
+    PT_CHECK(L.plain() || t->P.model == PT_TRANSE, PT_ENOTSUP,
+             "SigmoidLoss, adversarial weights and a model margin train TransE only (TransH is not implemented)");
+    t->loss = L;
+    return PT_OK;
+}
+
+extern "C" int pt_trainer_set_adam(pt_trainer *t, const pt_adam_state *a) {
+    PT_CHECK(t && a, PT_EINVAL, "pt_trainer_set_adam: null argument");
+    PT_CHECK(a->ent_m && a->ent_v && a->rel_m && a->rel_v && (t->P.model == PT_TRANSE || (a->norm_m && a->norm_v)),
+             PT_EINVAL, "Adam needs exp_avg and exp_avg_sq buffers for every table");
+    PT_CHECK(a->beta1 >= 0. && a->beta1 < 1. && a->beta2 >= 0. && a->beta2 < 1. && a->eps >= 0. && a->step >= 0,
+             PT_EINVAL, "Adam: betas must be in [0, 1), eps and step non-negative");
+    t->adam.m[0] = a->ent_m; t->adam.m[1] = a->rel_m; t->adam.m[2] = a->norm_m;
+    t->adam.v[0] = a->ent_v; t->adam.v[1] = a->rel_v; t->adam.v[2] = a->norm_v;
+    t->adam.beta1 = a->beta1; t->adam.beta2 = a->beta2; t->adam.eps = a->eps;
+    t->adam_step = a->step;
+    t->adam_set = true;
+    return PT_OK;
+}
+extern "C" int64_t pt_trainer_adam_step(const pt_trainer *t) { return t ? t->adam_step : -1; }
+
 extern "C" int pt_trainer_step(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, int64_t bern, int64_t filter,
                                const int64_t *d_bh, const int64_t *d_bt, const int64_t *d_br, float *d_loss,
                                void *stream) {
@@ -512,6 +586,7 @@ extern "C" int pt_trainer_step(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t
         PT_CHECK(d_bt && d_br, PT_EINVAL, "external batch needs h, t and r arrays");
         PT_CHECK(bs > 0 && neg > 0, PT_EINVAL, "batch_size and neg_ent must be positive");
         if (t->ordered) {
+            PT_CHECK(!t->extended(), PT_ENOTSUP, kExtendedMsg);
             int rc = ensure_ordered(t, bs * (1 + neg));
             if (rc) return rc;
             return enqueue_ordered(t, bs, neg, d_bh, d_bt, d_br, d_loss, 0, (hipStream_t)stream);
@@ -521,10 +596,45 @@ extern "C" int pt_trainer_step(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t
         return enqueue_external(t, bs, neg, d_bh, d_bt, d_br, d_loss, (hipStream_t)stream);
     }
     PT_CHECK(bs > 0 && neg > 0, PT_EINVAL, "batch_size and neg_ent must be positive");
+    PT_CHECK(!t->extended(), PT_ENOTSUP, kExtendedMsg);
     if (t->ordered) return enqueue_ordered_run(t, s, bs, neg, bern, filter, 1, d_loss, 0, (hipStream_t)stream);
     int rc = prepare_sampled(t, s, bs, neg);
     if (rc) return rc;
     return enqueue_run(t, s, bs, neg, bern, filter, 1, d_loss, (hipStream_t)stream);
+}
+
+// Measurement hook of the external-batch step: `steps` steps on one batch, events around both launches of each
+extern "C" int pt_trainer_steps_timed(pt_trainer *t, int64_t bs, int64_t neg, const int64_t *d_bh,
+                                      const int64_t *d_bt, const int64_t *d_br, int64_t steps, float *d_loss,
+                                      float *ms2, void *stream) {
+    PT_CHECK(t && d_bh && d_bt && d_br && ms2 && steps > 0, PT_EINVAL, "pt_trainer_steps_timed: bad argument");
+    PT_CHECK(bs > 0 && neg > 0, PT_EINVAL, "batch_size and neg_ent must be positive");
+    PT_CHECK(!t->ordered, PT_ENOTSUP, "pt_trainer_steps_timed times the fast path (reference-order mode is on)");
+    int rc = ensure_lpart(t, bs);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    Timing tm;   // (its pool only: the events are created up front and destroyed with it)
+    rc = tm.reserve((size_t)(3 * steps));
+    if (rc) return rc;
+    PT_HIP(pt::launch_spin(20000, st));   // hold the stream while the host enqueues every launch
+    for (int64_t i = 0; i < steps; ++i) {
+        rc = enqueue_external(t, bs, neg, d_bh, d_bt, d_br, d_loss, st, &tm.pool[(size_t)(3 * i)]);
+        if (rc) {   // the events of the launches already queued are destroyed with `tm`: let them finish first
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
+    }
+    PT_HIP(hipStreamSynchronize(st));
+    double tot[2] = {0, 0};
+    for (int64_t i = 0; i < steps; ++i)
+        for (int k = 0; k < 2; ++k) {
+            float ms = 0;
+            PT_HIP(hipEventElapsedTime(&ms, tm.pool[(size_t)(3 * i + k)], tm.pool[(size_t)(3 * i + k + 1)]));
+            tot[k] += ms;
+        }
+    ms2[0] = (float)(tot[0] / (double)steps);
+    ms2[1] = (float)(tot[1] / (double)steps);
+    return PT_OK;
 }
 
 // `steps` in-kernel-sampled steps launched one by one with an event pair around every launch on
@@ -534,6 +644,7 @@ extern "C" int pt_trainer_run_timed(pt_trainer *t, pt_sampler *s, int64_t bs, in
                                     int64_t filter, int64_t steps, float *d_losses, float *ms4, void *stream) {
     PT_CHECK(t && ms4 && steps > 0, PT_EINVAL, "pt_trainer_run_timed: bad argument");
     PT_CHECK(!t->ordered, PT_ENOTSUP, "pt_trainer_run_timed times the fast path (reference-order mode is on)");
+    PT_CHECK(!t->extended(), PT_ENOTSUP, kExtendedMsg);
     int rc = prepare_sampled(t, s, bs, neg);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -724,6 +835,7 @@ extern "C" int pt_trainer_run(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t 
                               int64_t steps, float *d_losses, void *stream) {
     PT_CHECK(t && d_losses, PT_EINVAL, "pt_trainer_run: null argument");
     PT_CHECK(steps > 0, PT_EINVAL, "steps must be positive");
+    PT_CHECK(!t->extended(), PT_ENOTSUP, kExtendedMsg);
     if (t->ordered) {
         PT_CHECK(bs > 0 && neg > 0, PT_EINVAL, "batch_size and neg_ent must be positive");
         return enqueue_ordered_run(t, s, bs, neg, bern, filter, steps, d_losses, 1, (hipStream_t)stream);

@@ -21,7 +21,8 @@ c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_f32p = ctypes.POINTER(ctypes.c_float)
 
 PT_TRANSE, PT_TRANSH = 0, 1
-PT_SGD, PT_ADAGRAD = 0, 1
+PT_SGD, PT_ADAGRAD, PT_ADAM = 0, 1, 2
+PT_LOSS_MARGIN, PT_LOSS_SIGMOID = 0, 1
 PT_DETERMINISTIC = 1   # pt_universes_train_ex flag: reference-order (deterministic) mode
 # sampling paths of the counting-sort (large neg) step (include/putranse.h PT_PATH_*)
 PT_PATH_TWO_PASS, PT_PATH_FUSED, PT_PATH_PART, PT_PATH_SAMPLED = 0, 1, 2, 3
@@ -37,6 +38,19 @@ class ModelDesc(ctypes.Structure):
     _fields_ = [("model", c_i32), ("p_norm", c_i32), ("norm_flag", c_i32), ("opt", c_i32), ("lr", c_f32),
                 ("margin", c_f32), ("ent_total", c_i64), ("rel_total", c_i64), ("dim", c_i64), ("ent", c_vp),
                 ("rel", c_vp), ("normv", c_vp), ("ent_acc", c_vp), ("rel_acc", c_vp), ("norm_acc", c_vp)]
+
+
+class LossDesc(ctypes.Structure):
+    """pt_loss_desc: loss of the external-batch step (pt_trainer_set_loss)."""
+    _fields_ = [("kind", c_i32), ("adv", c_i32), ("temperature", c_f32), ("score_margin_flag", c_i32),
+                ("score_margin", c_f32)]
+
+
+class AdamState(ctypes.Structure):
+    """pt_adam_state: exp_avg / exp_avg_sq per table, betas, eps, steps done (pt_trainer_set_adam)."""
+    _fields_ = [("ent_m", c_vp), ("rel_m", c_vp), ("norm_m", c_vp), ("ent_v", c_vp), ("rel_v", c_vp),
+                ("norm_v", c_vp), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("step", c_i64)]
 
 
 class UniverseJob(ctypes.Structure):
@@ -99,6 +113,10 @@ SIGNATURES = {
     "pt_universe_dim_supported": (ctypes.c_int, [c_i64, c_i32]),
     "pt_trainer_step_apply": (ctypes.c_int, [c_vp]),   # shim: 0
     "pt_trainer_get_deterministic": (ctypes.c_int, [c_vp]),
+    "pt_trainer_set_loss": (ctypes.c_int, [c_vp, ctypes.POINTER(LossDesc)]),
+    "pt_trainer_set_adam": (ctypes.c_int, [c_vp, ctypes.POINTER(AdamState)]),
+    "pt_trainer_adam_step": (c_i64, [c_vp]),
+    "pt_trainer_steps_timed": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "pt_trainer_sample_csr": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, ctypes.c_int32, c_vp,
                                              c_vp, c_vp, c_vp, c_vp]),
     "pt_score": (ctypes.c_int, [ctypes.POINTER(ModelDesc), c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),

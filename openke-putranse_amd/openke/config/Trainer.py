@@ -7,7 +7,9 @@ kernel from the data loader's stream (bit-identical to TrainDataLoader.sampling(
 NegativeSampling + MarginLoss forward and the analytic backward, and applies SGD or Adagrad to the
 touched rows only (identical to the reference's dense update). Losses stay on the device until the
 end of the epoch (one host sync per epoch instead of one per step). Cross sampling and relation
-corruption (neg_rel > 0) train batch by batch: GPU-sampled batch, then the external-batch step."""
+corruption (neg_rel > 0) train batch by batch: GPU-sampled batch, then the external-batch step. So do
+TransE under SigmoidLoss, the self-adversarial weights (adv_temperature) or a model margin (k_step_adv),
+and Adam (k_apply_adam, dense) for either model."""
 import ctypes
 import os
 
@@ -16,20 +18,27 @@ import torch
 from tqdm import tqdm
 
 from .. import _native
-from ..module.loss import MarginLoss
+from ..module.loss import MarginLoss, SigmoidLoss
 from ..module.model.Model import Model
 from ..module.strategy import NegativeSampling
 
 
 class NativeOptimizer(object):
-    """Optimizer state of the fused path (Adagrad state_sum per table, eps 1e-10, lr_decay 0,
-    initial accumulator 0 — torch.optim.Adagrad defaults used by Trainer.py:64-70)."""
+    """Optimizer state of the native path: Adagrad state_sum per table (eps 1e-10, lr_decay 0, initial
+    accumulator 0 — torch.optim.Adagrad defaults used by Trainer.py:64-70), or Adam's exp_avg / exp_avg_sq per
+    table and the shared step count (betas (0.9, 0.999), eps 1e-8 — torch.optim.Adam defaults, Trainer.py:77-82)."""
 
     def __init__(self, method, lr, tables):
         self.method = method
         self.lr = lr
         self.state_sum = tuple(torch.zeros_like(t) if (t is not None and method == _native.PT_ADAGRAD) else None
                                for t in tables)
+        adam = method == _native.PT_ADAM
+        self.exp_avg = tuple(torch.zeros_like(t) if (t is not None and adam) else None for t in tables)
+        self.exp_avg_sq = tuple(torch.zeros_like(t) if (t is not None and adam) else None for t in tables)
+        self.betas = (0.9, 0.999)
+        self.eps = 1e-8
+        self.step = 0
 
     def zero_grad(self):
         pass
@@ -65,13 +74,22 @@ class Trainer(object):
         kge, loss = ns.model, ns.loss
         if not isinstance(kge, Model) or kge.native_model is None:
             raise NotImplementedError("model %s is outside the accelerated path" % type(kge).__name__)
-        if not isinstance(loss, MarginLoss) or loss.adv_flag:
-            raise NotImplementedError("only MarginLoss without adversarial temperature is accelerated")
+        if not isinstance(loss, (MarginLoss, SigmoidLoss)):
+            raise NotImplementedError("loss %s is outside the accelerated path (MarginLoss and SigmoidLoss are)"
+                                      % type(loss).__name__)
+        if self._weighted(kge, loss) and kge.native_model != _native.PT_TRANSE:
+            raise NotImplementedError("SigmoidLoss, adversarial temperature and a model margin are accelerated for "
+                                      "TransE only")
         if ns.regul_rate != 0 or ns.l3_regul_rate != 0:
             raise NotImplementedError("regularisation is outside the accelerated path")
         if self.lr_decay != 0 or self.weight_decay != 0:
             raise NotImplementedError("lr_decay / weight_decay are 0 in the reference path")
         return ns, kge, loss
+
+    @staticmethod
+    def _weighted(kge, loss):
+        """Whether the step is outside plain MarginLoss on the raw distance (then k_step_adv computes it)."""
+        return isinstance(loss, SigmoidLoss) or bool(loss.adv_flag) or bool(getattr(kge, "margin_flag", False))
 
     def _setup(self):
         _native.require_gpu()
@@ -81,13 +99,19 @@ class Trainer(object):
             m = self.opt_method
             if m in ("Adagrad", "adagrad"):
                 method = _native.PT_ADAGRAD
-            elif m in ("Adadelta", "adadelta", "Adam", "adam"):
-                raise NotImplementedError("%s is outside the accelerated path (SGD and Adagrad are)" % m)
+            elif m in ("Adam", "adam"):
+                method = _native.PT_ADAM
+            elif m in ("Adadelta", "adadelta"):
+                raise NotImplementedError("%s is outside the accelerated path (SGD, Adagrad and Adam are)" % m)
             else:
                 method = _native.PT_SGD
             self.optimizer = NativeOptimizer(method, self.alpha, kge.tables())
         opt = self.optimizer
-        margin = float(loss.margin.item())
+        weighted = self._weighted(kge, loss)
+        if self.deterministic and (weighted or opt.method == _native.PT_ADAM):
+            raise NotImplementedError("deterministic=True (reference-order mode) covers plain MarginLoss with SGD or "
+                                      "Adagrad only")
+        margin = float(loss.margin.item()) if isinstance(loss, MarginLoss) else 0.0
         desc = kge.native_desc(opt.method, opt.lr, margin, opt.state_sum)
         key = (id(kge), kge.tables()[0].data_ptr(), opt.method, opt.lr, margin)
         L = _native.lib()
@@ -99,7 +123,30 @@ class Trainer(object):
             _native.check(L.pt_trainer_update_desc(self._native, ctypes.byref(desc)))
         self._native_key = key
         _native.check(L.pt_trainer_set_deterministic(self._native, 1 if self.deterministic else 0))
+        ld = _native.LossDesc()
+        ld.kind = _native.PT_LOSS_SIGMOID if isinstance(loss, SigmoidLoss) else _native.PT_LOSS_MARGIN
+        ld.adv = 1 if loss.adv_flag else 0
+        ld.temperature = float(loss.adv_temperature.item()) if loss.adv_flag else 0.0
+        ld.score_margin_flag = 1 if getattr(kge, "margin_flag", False) else 0
+        ld.score_margin = float(kge.margin.item()) if ld.score_margin_flag else 0.0
+        _native.check(L.pt_trainer_set_loss(self._native, ctypes.byref(ld)))
+        if opt.method == _native.PT_ADAM:
+            a = _native.AdamState()
+            a.ent_m, a.rel_m, a.norm_m = (_native.ptr(x) for x in opt.exp_avg)
+            a.ent_v, a.rel_v, a.norm_v = (_native.ptr(x) for x in opt.exp_avg_sq)
+            a.beta1, a.beta2 = opt.betas
+            a.eps = opt.eps
+            a.step = int(opt.step)
+            _native.check(L.pt_trainer_set_adam(self._native, ctypes.byref(a)))
         return ns, kge, loss
+
+    def _external_only(self, kge, loss):
+        """Whether every step goes through the external-batch step (k_step / k_step_adv + k_apply / k_apply_adam)."""
+        return self._weighted(kge, loss) or self.optimizer.method == _native.PT_ADAM
+
+    def _sync_step(self):
+        if self.optimizer.method == _native.PT_ADAM:
+            self.optimizer.step = int(_native.lib().pt_trainer_adam_step(self._native))
 
     def __del__(self):
         if getattr(self, "_native", None) is not None:
@@ -142,6 +189,7 @@ class Trainer(object):
         _native.check(_native.lib().pt_trainer_step(self._native, None, bs, neg, 0, 0, _native.ptr(h),
                                                     _native.ptr(t), _native.ptr(r), _native.ptr(out),
                                                     _native.stream()))
+        self._sync_step()
         return out.item()
 
     def _run_batches(self, L, sampler, bern, bs, nb, losses, buf):
@@ -182,7 +230,7 @@ class Trainer(object):
         bern = L.pt_legacy_bern()
         dev = kge.ent_embeddings.weight.device
         losses = torch.zeros(max(nb, 1), dtype=torch.float32, device=dev)
-        fused = dl.sampling_mode == "normal" and dl.negative_rel == 0
+        fused = dl.sampling_mode == "normal" and dl.negative_rel == 0 and not self._external_only(kge, loss)
         buf = None
         if not fused:
             seq = bs * (1 + neg + dl.negative_rel)
@@ -190,6 +238,7 @@ class Trainer(object):
                 (torch.zeros(seq, dtype=torch.float32, device=dev),)
         print("Finish initializing...")
         training_range = tqdm(range(self.train_times))
+        self.epoch_losses = []   # summed step losses of every epoch of this run
         for epoch in training_range:
             if nb > 0 and fused:
                 _native.check(L.pt_trainer_run(self._native, sampler, bs, neg, bern, dl.filter, nb,
@@ -197,9 +246,11 @@ class Trainer(object):
             elif nb > 0:
                 losses.zero_()
                 self._run_batches(L, sampler, bern, bs, nb, losses, buf)
+                self._sync_step()
             host = losses.cpu().numpy()
             self.last_step_losses = host[:nb].copy()
             res = float(host[:nb].sum())
+            self.epoch_losses.append(res)
             loss_v = float(host[nb - 1]) if nb > 0 else 0.0
             training_range.set_description("Epoch %d | loss: %f" % (epoch, loss_v))
             if self.save_steps and self.checkpoint_dir and (epoch + 1) % self.save_steps == 0:
