@@ -135,14 +135,13 @@ hipError_t launch_apply_adam(const StepParams &P, const StepWorkspace &W, const 
     for (int i = 0; i < A.ntab; ++i) rows += A.t[i].rows;
     const int64_t gpb = 256 / s.G;
     const dim3 grid((unsigned)((rows + gpb - 1) / gpb)), block(256);
-#define PT_ADAM_K(G_, V_, K_)                                                          \
-    if (s.G == G_ && s.VEC == V_ && s.KCH == K_) {                                    \
-        hipLaunchKernelGGL((dev::k_apply_adam<G_, V_, K_>), grid, block, 0, st, A);   \
-        return hipGetLastError();                                                     \
-    }
-    PT_SHAPES(PT_ADAM_K)
-#undef PT_ADAM_K
-    return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;
+    for_shape(s, [&](auto sh) {
+        using T = decltype(sh);
+        hipLaunchKernelGGL((dev::k_apply_adam<T::G, T::VEC, T::KCH>), grid, block, 0, st, A);
+        e = hipGetLastError();
+    });
+    return e;
 }
 
 }  // namespace pt

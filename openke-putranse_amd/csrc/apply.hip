@@ -1,10 +1,7 @@
 // HIP kernels of the optimizer apply pass (sparse SGD / Adagrad rows) for gfx950.
 //
 // Layout and mapping
-//  * Tables are row-major fp32 [rows][dim]. A "lane group" of G lanes (G | 64, a power of two) owns one
-//    row-sized vector: lane l holds chunks c = k*G + l (k < KCH) of VEC consecutive floats, so a row is
-//    read with fully coalesced 16-B (VEC=4) or 4-B (VEC=1) accesses and every reduction is a shuffle
-//    butterfly inside the group. One positive triple and all its negatives belong to one group.
+//  * Rows are held by lane groups (struct Shape, kernels.h); one group applies one table row.
 //  * This is gather/axpy work (no dense contraction): the roofline is HBM / Infinity-Cache bandwidth
 //    and the memory-side float-atomic rate, not MFMA.
 //
@@ -271,40 +268,28 @@ hipError_t launch_apply(const StepParams &P, const StepWorkspace &W, uint64_t *s
     A.loss_assign = P.loss_assign;
     int64_t rows = 0;
     for (int i = 0; i < A.ntab; ++i) rows += A.t[i].rows;
-    // float4 rows through raw buffers where the offsets fit 31 bits, else the kernels below
-    int64_t con_rows = 0;
-    if (csr) con_rows = P.batch_size * P.neg;
-    const bool fits31 = (P.ent_total + P.rel_total + con_rows) * P.dim * 4 < (int64_t(1) << 31);
-    if (P.dim % 4 == 0 && fits31) {
-        const int64_t chunks = P.dim / 4;
-        int G = 2;
-        while (G < chunks && G < 64) G <<= 1;
-        const int KCH = (int)((chunks + G - 1) / G);
-        // contribution rows in flight per lane group: 8 for one-chunk float4 rows (C2: the bucket of a row
-        // - Poisson, mean 3.6 at C2 - mostly in one round trip; measured 12.0 vs 12.6 us), else 4
-        const int nc = G == 64 && KCH == 1 ? 8 : 4;
-        const int64_t gpb4 = 256 / G;
-        const dim3 grid((unsigned)((rows + gpb4 - 1) / gpb4)), block(256);
-#define PT_APPLYB(G_, K_, N_)                                                              \
-        if (G == G_ && KCH == K_ && nc == N_) {                                           \
-            hipLaunchKernelGGL((dev::k_apply_buf<G_, 4, K_, N_>), grid, block, 0, st, A); \
-            return hipGetLastError();                                                     \
-        }
-        // every (G, KCH) of a supported dim (shape_supported: dim / 4 <= 128 chunks, so KCH <= 2)
-        PT_APPLYB(2, 1, 4) PT_APPLYB(4, 1, 4) PT_APPLYB(8, 1, 4) PT_APPLYB(16, 1, 4) PT_APPLYB(32, 1, 4)
-        PT_APPLYB(64, 1, 8) PT_APPLYB(64, 2, 4)
-#undef PT_APPLYB
-    }
+    // float4 rows through raw buffers (k_apply_buf) where the offsets fit 31 bits - the contribution rows count
+    // only when there are any - else k_apply
+    const bool buf = P.dim % 4 == 0 && offsets_fit31(P, csr ? P.batch_size * P.neg : 0);
     const int64_t gpb = 256 / s.G;
     const dim3 grid((unsigned)((rows + gpb - 1) / gpb)), block(256);
-#define PT_APPLY(G_, V_, K_)                                                                  \
-    if (s.G == G_ && s.VEC == V_ && s.KCH == K_) {                                          \
-        hipLaunchKernelGGL((dev::k_apply<G_, V_, K_>), grid, block, 0, st, A);              \
-        return hipGetLastError();                                                           \
-    }
-    PT_SHAPES(PT_APPLY)
-#undef PT_APPLY
-    return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;
+    for_shape(s, [&](auto sh) {
+        using T = decltype(sh);
+        if constexpr (T::VEC == 4) {
+            // contribution rows in flight per lane group: 8 for one-chunk float4 rows (C2: the bucket of a row
+            // - Poisson, mean 3.6 at C2 - mostly in one round trip; measured 12.0 vs 12.6 us), else 4
+            constexpr int NC = T::G == 64 && T::KCH == 1 ? 8 : 4;
+            if (buf) {
+                hipLaunchKernelGGL((dev::k_apply_buf<T::G, 4, T::KCH, NC>), grid, block, 0, st, A);
+                e = hipGetLastError();
+                return;
+            }
+        }
+        hipLaunchKernelGGL((dev::k_apply<T::G, T::VEC, T::KCH>), grid, block, 0, st, A);
+        e = hipGetLastError();
+    });
+    return e;
 }
 
 }  // namespace pt

@@ -1,6 +1,6 @@
-// Device-side building blocks shared by the HIP kernels (kernels.hip, universe.hip): lane-group row
+// Device-side building blocks shared by the HIP kernels (the .hip files and universes_kern.h): lane-group row
 // vectors with DPP reductions, the reference sampler restated per draw, and the fused per-positive
-// forward/backward (group_step). See kernels.hip for the layout notes.
+// forward/backward (group_step). The lane-group layout is described at struct Shape (kernels.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "graph.h"
 
@@ -70,12 +71,18 @@ struct LpPair {
     int32_t key, universe, anchor, rel, side;   // local anchor entity / relation ids
 };
 
-// lane-group shape of a row of D floats: G lanes x KCH chunks of VEC floats (kernels.hip header)
+// Lane-group shape of a row of D floats. Tables are row-major fp32 [rows][dim]. A "lane group" of G lanes (G | 64,
+// a power of two) owns one row-sized vector: lane l holds chunks c = k*G + l (k < KCH) of VEC consecutive floats,
+// so a row is read with fully coalesced 16-B (VEC=4) or 4-B (VEC=1) accesses and every reduction is a shuffle
+// butterfly inside the group.
 struct Shape {
     int G, VEC, KCH;
 };
 
-inline Shape pick_shape(int64_t D, bool vec4 = true) {
+// The shape of a dim-D row: float4 chunks when vec4 and D % 4 == 0, else single floats. For D % 4 == 0 this is
+// G = the smallest power of two in [2, 64] that is >= D / 4 (64 beyond), KCH = ceil(D / 4 / G): the rule of the
+// float4-only kernels (k_step_csr, k_apply_buf), which therefore take pick_shape(D) as it is.
+constexpr Shape pick_shape(int64_t D, bool vec4 = true) {
     const int VEC = vec4 && D % 4 == 0 ? 4 : 1;
     const int64_t chunks = D / VEC;
     int G = 1;
@@ -95,6 +102,30 @@ inline Shape pick_shape(int64_t D, bool vec4 = true) {
     X(2, 4, 1) X(4, 4, 1) X(8, 4, 1) X(16, 4, 1) X(32, 4, 1) X(64, 4, 1) X(64, 4, 2)                 \
     X(2, 1, 1) X(4, 1, 1) X(8, 1, 1) X(16, 1, 1) X(32, 1, 1) X(64, 1, 1) X(64, 1, 2) X(64, 1, 4)    \
     X(64, 1, 8)
+
+// Run-time values to template arguments, for the launchers: for_shape calls f(ShapeTag<G, VEC, KCH>{}) for the
+// PT_SHAPES entry equal to s, for_value<Vs...> calls f(std::integral_constant<int, V>{}) for the V equal to v
+// (model 0/1, p_norm 1/2, booleans, ...); both return whether one matched. f is a generic lambda that names the
+// kernel instance from its argument's type; a kernel with float4 rows only filters with if constexpr (T::VEC == 4).
+template <int G_, int VEC_, int KCH_>
+struct ShapeTag {
+    static constexpr int G = G_, VEC = VEC_, KCH = KCH_;
+};
+template <typename F>
+constexpr bool for_shape(const Shape &s, F &&f) {
+#define PT_FOR_SHAPE(G_, V_, K_)                    \
+    if (s.G == G_ && s.VEC == V_ && s.KCH == K_) { \
+        f(ShapeTag<G_, V_, K_>{});                  \
+        return true;                                \
+    }
+    PT_SHAPES(PT_FOR_SHAPE)
+#undef PT_FOR_SHAPE
+    return false;
+}
+template <int... Vs, typename F>
+constexpr bool for_value(int v, F &&f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
 
 bool shape_supported(int64_t dim);
 hipError_t launch_sample(const DeviceGraph &g, const uint64_t *states, int64_t threads, int64_t bs, int64_t neg,
@@ -122,6 +153,11 @@ hipError_t launch_sample_part(const DeviceGraph &g, uint64_t *states, int64_t th
                               hipStream_t st, int64_t call0 = 0, int advance = 1);
 hipError_t launch_scan_counts(const CsrWork &w, int64_t n, int64_t calls, uint64_t *states, int64_t threads,
                               int64_t bs, int64_t dpp, hipStream_t st);
+// the raw-buffer kernels (k_step_csr, k_apply_buf) address the ent / rel tables and con_rows contribution rows with
+// byte offsets that must fit 31 bits
+inline bool offsets_fit31(const StepParams &P, int64_t con_rows) {
+    return (P.ent_total + P.rel_total + con_rows) * P.dim * 4 < (int64_t(1) << 31);
+}
 bool step_fits(const StepParams &P, int64_t neg, bool csr);
 hipError_t launch_step(const StepParams &P, const DeviceGraph &g, const uint64_t *states, int64_t threads, int bern,
                        int filter, const int64_t *bh, const int64_t *bt, const int64_t *br, const StepWorkspace &W,

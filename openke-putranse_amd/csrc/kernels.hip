@@ -1,10 +1,7 @@
 // HIP kernels of the PuTransE / TransE / TransH hot path for gfx950 (MI355X).
 //
 // Layout and mapping
-//  * Tables are row-major fp32 [rows][dim]. A "lane group" of G lanes (G | 64, a power of two) owns one
-//    row-sized vector: lane l holds chunks c = k*G + l (k < KCH) of VEC consecutive floats, so a row is
-//    read with fully coalesced 16-B (VEC=4) or 4-B (VEC=1) accesses and every reduction is a shuffle
-//    butterfly inside the group. One positive triple and all its negatives belong to one group.
+//  * Rows are held by lane groups (struct Shape, kernels.h).
 //  * This is gather/axpy work (no dense contraction): the roofline is HBM / Infinity-Cache bandwidth
 //    and the memory-side float-atomic rate, not MFMA.
 //
@@ -709,9 +706,9 @@ __global__ __launch_bounds__(256) void k_score_queries(StepParams P, int side, c
 // k_lp_bases: one lane group per pair: the pair's normalized (projected for TransH) anchor combined
 //   with its relation -> base[pair][D] (+ the relation's normal for TransH), and the null_vector tuple
 //   score of the key in this universe (calc_tuple_score, :378-388: raw anchor, no projection).
-// k_lp_scan: one workgroup per (entity chunk, universe): each entity row is loaded (and, for TransE,
+// k_lp_scan_t: one workgroup per (tile of 64 entities, universe): each entity row is loaded (and, for TransE,
 //   normalized) ONCE and scored against every pair of its universe - the universe's rows are read once
-//   per chunk instead of once per pair.
+//   per tile instead of once per pair.
 // One launch pair covers every universe whose dim takes the same lane-group shape (each universe's own dim
 // at run time); the pairs' base / normal rows are `ds` floats apart (the largest dim of the launch).
 template <int MODEL, int G, int VEC, int KCH>
@@ -754,66 +751,9 @@ __global__ __launch_bounds__(256) void k_lp_bases(const LpUniverseDev *__restric
     vstore(b, base + pi * ds, D, lane);
 }
 
-template <int MODEL, int G, int VEC, int KCH>
-__global__ __launch_bounds__(256) void k_lp_scan(const LpUniverseDev *__restrict__ us, const LpPair *__restrict__ pairs,
-                                                 const int64_t *__restrict__ uoff, const int32_t *__restrict__ uids,
-                                                 int p_norm, int norm_flag, int64_t global_E, int64_t ds,
-                                                 const float *__restrict__ base, const float *__restrict__ normal,
-                                                 float *__restrict__ rows) {
-    using Vec = V<G, VEC, KCH>;
-    constexpr int GPB = 256 / G;
-    constexpr int EPG = 4;   // entities per lane group: each pair's base row is loaded once per 4 entities
-    const int lane = threadIdx.x % G;
-    const int grp = threadIdx.x / G;
-    const int32_t u = uids[blockIdx.y];
-    const LpUniverseDev U = us[u];
-    const int D = (int)U.dim;
-    const int64_t p0 = uoff[2 * u], p1 = uoff[2 * u + 1];   // the universe's pairs (relative to `pairs`)
-    const int64_t stride = (int64_t)gridDim.x * GPB * EPG;
-    for (int64_t e0 = ((int64_t)blockIdx.x * GPB + grp) * EPG; e0 < U.ent_total; e0 += stride) {
-        Vec X[EPG], xh[EPG];
-        int64_t col[EPG];
-#pragma unroll
-        for (int q = 0; q < EPG; ++q) {
-            const int64_t e = e0 + q < U.ent_total ? e0 + q : U.ent_total - 1;   // tail: repeat the last row
-            vload(X[q], U.ent + e * D, D, lane);
-            col[q] = e0 + q < U.ent_total ? U.remap[e] : -1;
-        }
-        if constexpr (MODEL == 0) {
-#pragma unroll
-            for (int q = 0; q < EPG; ++q) {
-                if (norm_flag) vnormalize(X[q], xh[q]); else xh[q] = X[q];
-            }
-        }
-        for (int64_t pi = p0; pi < p1; ++pi) {
-            const LpPair pr = pairs[pi];
-            Vec b;
-            vload(b, base + pi * ds, D, lane);
-            Vec nW;
-            if constexpr (MODEL == 1) vload(nW, normal + pi * ds, D, lane);
-#pragma unroll
-            for (int q = 0; q < EPG; ++q) {
-                if constexpr (MODEL == 1) {
-                    Vec xp;
-                    const float xd = vdot(X[q], nW);
-#pragma unroll
-                    for (int k = 0; k < Vec::N; ++k) xp.x[k] = X[q].x[k] - xd * nW.x[k];
-                    if (norm_flag) vnormalize(xp, xh[q]); else xh[q] = xp;
-                }
-                Vec v;
-#pragma unroll
-                for (int k = 0; k < Vec::N; ++k) v.x[k] = pr.side == 0 ? xh[q].x[k] + b.x[k] : b.x[k] - xh[q].x[k];
-                const float sc = vpnorm(v, p_norm);
-                if (lane == 0 && col[q] >= 0)
-                    atomicMin(reinterpret_cast<int *>(rows + (int64_t)pr.key * global_E + col[q]), __float_as_int(sc));
-            }
-        }
-    }
-}
-
-// k_lp_scan_t: the scan transposed - one LANE per entity. A workgroup (4 waves) stages a tile of 64
-// consecutive local entity rows in LDS once (row stride D + 1 floats: lane e reading float d of its row hits
-// bank (e + d) mod 64, conflict-free), and each wave walks a quarter of the universe's pairs: for a pair, every
+// k_lp_scan_t: the scan, transposed against the lane-group kernels - one LANE per entity. A workgroup (NW waves)
+// stages a tile of 64 consecutive local entity rows in LDS once (row stride D + 1 floats: lane e reading float d of
+// its row hits bank (e + d) mod 64, conflict-free), and each wave walks every NW-th of the universe's pairs: for a pair, every
 // lane sums its own entity's |x + b| (or squares) sequentially over d with the pair's base row uniform across
 // the wave - no cross-lane reduction per score - and MINs its score into the key row with one atomic
 // instruction for 64 entities, skipped when the row already holds a score no larger (the rows only decrease,
@@ -884,9 +824,7 @@ __device__ __forceinline__ void sum8xn(int D, F f, float (&r)[NP]) {
 }
 
 #ifndef PT_LP_PAIRS
-#ifndef PT_LP_PAIRS
 #define PT_LP_PAIRS 2   // (measured r05, C4 k_lp_scan_t total: 1 pair 137.9 ms, 2 pairs 99.4, 4 pairs 105.3, 8 pairs 128.5)
-#endif
 #endif
 
 template <int MODEL, int NW>
@@ -1007,16 +945,19 @@ __global__ __launch_bounds__(64 * NW) void k_lp_scan_t(const LpUniverseDev *__re
 }  // namespace dev
 
 // ==================================================================== host launchers ===========
-bool shape_supported(int64_t dim) {
-    if (dim <= 0) return false;
-    bool a = false, b = false;
-    const Shape s = pick_shape(dim), s1 = pick_shape(dim, false);
-#define PT_SUP(g, v, k) if (s.G == g && s.VEC == v && s.KCH == k) a = true; \
-                        if (s1.G == g && s1.VEC == v && s1.KCH == k) b = true;
-    PT_SHAPES(PT_SUP)
-#undef PT_SUP
-    return a && b;
+constexpr bool shape_listed(const Shape &s) { return for_shape(s, [](auto) {}); }
+constexpr bool dim_dispatches(int64_t dim) {
+    return shape_listed(pick_shape(dim)) && shape_listed(pick_shape(dim, false));
 }
+// every dim up to 512 has its instances under both layouts; the first dims past it (VEC = 1, VEC = 4) do not
+constexpr bool dims_1_to_512_dispatch() {
+    for (int64_t dim = 1; dim <= 512; ++dim)
+        if (!dim_dispatches(dim)) return false;
+    return !dim_dispatches(513) && !dim_dispatches(516);
+}
+static_assert(dims_1_to_512_dispatch(), "PT_SHAPES does not cover pick_shape over dims 1..512");
+
+bool shape_supported(int64_t dim) { return dim > 0 && dim_dispatches(dim); }
 
 hipError_t launch_sample(const DeviceGraph &g, const uint64_t *states, int64_t threads, int64_t bs, int64_t neg,
                          int64_t neg_rel, int mode, int bern, int filter, int64_t *h, int64_t *t, int64_t *r, float *y,
@@ -1135,17 +1076,16 @@ hipError_t launch_score(const StepParams &P, int mode, const int64_t *h, const i
     const Shape s = pick_shape(P.dim);
     const int64_t gpb = 256 / s.G;
     const dim3 grid((unsigned)((n + gpb - 1) / gpb)), block(256);
-#define PT_SCORE(G_, V_, K_)                                                                                     \
-    if (s.G == G_ && s.VEC == V_ && s.KCH == K_) {                                                             \
-        if (P.model == 0)                                                                                        \
-            hipLaunchKernelGGL((dev::k_score<0, G_, V_, K_>), grid, block, 0, st, P, mode, h, t, r, n, out);     \
-        else                                                                                                     \
-            hipLaunchKernelGGL((dev::k_score<1, G_, V_, K_>), grid, block, 0, st, P, mode, h, t, r, n, out);     \
-        return hipGetLastError();                                                                              \
-    }
-    PT_SHAPES(PT_SCORE)
-#undef PT_SCORE
-    return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;
+    for_shape(s, [&](auto sh) {
+        for_value<0, 1>(P.model != 0, [&](auto m) {
+            using T = decltype(sh);
+            hipLaunchKernelGGL((dev::k_score<m.value, T::G, T::VEC, T::KCH>), grid, block, 0, st, P, mode, h, t, r, n,
+                               out);
+            e = hipGetLastError();
+        });
+    });
+    return e;
 }
 
 hipError_t launch_score_queries(const StepParams &P, int side, const int64_t *qh, const int64_t *qt, const int64_t *qr,
@@ -1156,99 +1096,54 @@ hipError_t launch_score_queries(const StepParams &P, int side, const int64_t *qh
     int64_t bx = (E + gpb - 1) / gpb;
     if (bx > 128) bx = 128;
     const dim3 grid((unsigned)bx, (unsigned)nq), block(256);
-#define PT_SQ(G_, V_, K_)                                                                                            \
-    if (s.G == G_ && s.VEC == V_ && s.KCH == K_) {                                                                 \
-        if (P.model == 0)                                                                                            \
-            hipLaunchKernelGGL((dev::k_score_queries<0, G_, V_, K_>), grid, block, 0, st, P, side, qh, qt, qr, nq, E, \
-                               out, global_order);                                                                   \
-        else                                                                                                         \
-            hipLaunchKernelGGL((dev::k_score_queries<1, G_, V_, K_>), grid, block, 0, st, P, side, qh, qt, qr, nq, E, \
-                               out, global_order);                                                                   \
-        return hipGetLastError();                                                                                  \
-    }
-    PT_SHAPES(PT_SQ)
-#undef PT_SQ
-    return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;
+    for_shape(s, [&](auto sh) {
+        for_value<0, 1>(P.model != 0, [&](auto m) {
+            using T = decltype(sh);
+            hipLaunchKernelGGL((dev::k_score_queries<m.value, T::G, T::VEC, T::KCH>), grid, block, 0, st, P, side, qh,
+                               qt, qr, nq, E, out, global_order);
+            e = hipGetLastError();
+        });
+    });
+    return e;
 }
 
-// PT_LP_SCAN_T (measurement builds): 1 = the transposed scan k_lp_scan_t (default), 0 = k_lp_scan
-#ifndef PT_LP_SCAN_T
-#define PT_LP_SCAN_T 1
-#endif
-// k_lp_scan_t's waves per workgroup sharing one tile (PT_LP_WAVES = 4 | 8 | 16 in the tuning build; measured r05,
-// C4's nine launches: 4 waves 85.3 ms, 8 waves 77.1 ms, 16 waves 91.3 ms, profiles/r05_c4_lp_waves.json)
-static int lp_waves() {
-    static const int nw = [] {
-        const char *v = pt_tuning_env("PT_LP_WAVES");
-        const int x = v ? atoi(v) : 8;
-        return x == 4 || x == 16 ? x : 8;
-    }();
-    return nw;
-}
+// k_lp_scan_t's waves per workgroup sharing one tile (measured r05, C4's nine launches: 4 waves 85.3 ms, 8 waves
+// 77.1 ms, 16 waves 91.3 ms, profiles/r05_c4_lp_waves.json)
+static constexpr int kLpWaves = 8;
+
 hipError_t launch_lp_min(const LpUniverseDev *us, const LpPair *pairs, int64_t n_pairs, const int64_t *uoff,
                          const int32_t *uids, int64_t n_active, int64_t dim, int64_t max_ent, int model, int p_norm,
                          int norm_flag, int64_t global_E, int64_t ds, float *base, float *normal, float *rows,
                          float *tuple_min, hipStream_t st) {
     if (n_pairs <= 0) return hipSuccess;
     const Shape s = pick_shape(dim);
-    // the transposed scan's tile of 64 rows in LDS (row stride dim + 1)
+    // the scan's tile of 64 rows in LDS (row stride dim + 1): at most 64 * 513 floats = 128 KB at a dispatched dim
     const size_t lds_t = sizeof(float) * 64 * (size_t)(dim + 1);
-    const int nw = lp_waves();
-    if (PT_LP_SCAN_T && lds_t > (64 << 10) && lds_t <= (160 << 10)) {
-        const void *fn[6] = {reinterpret_cast<const void *>(dev::k_lp_scan_t<0, 4>),
-                             reinterpret_cast<const void *>(dev::k_lp_scan_t<1, 4>),
-                             reinterpret_cast<const void *>(dev::k_lp_scan_t<0, 8>),
-                             reinterpret_cast<const void *>(dev::k_lp_scan_t<1, 8>),
-                             reinterpret_cast<const void *>(dev::k_lp_scan_t<0, 16>),
-                             reinterpret_cast<const void *>(dev::k_lp_scan_t<1, 16>)};
-        const int k = nw == 4 ? 0 : nw == 8 ? 2 : 4;
-        for (int m = 0; m < 2; ++m) {
-            const hipError_t e = hipFuncSetAttribute(fn[k + m], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
-            if (e != hipSuccess) return e;
-        }
-    }
     const int64_t gpb = 256 / s.G;
-    const dim3 gb((unsigned)((n_pairs + gpb - 1) / gpb)), block(256);
-    int64_t bx = (max_ent + gpb * 4 - 1) / (gpb * 4);
-    if (bx > 32) bx = 32;
-    if (bx < 1) bx = 1;
-#define PT_LPT(NW_)                                                                                                \
-    if (nw == NW_) {                                                                                               \
-        if (model == 0)                                                                                            \
-            hipLaunchKernelGGL((dev::k_lp_scan_t<0, NW_>), gt, bt, lds_t, st, us, pairs, uoff, uids + y0, p_norm,    \
-                               norm_flag, global_E, ds, base, normal, rows);                                       \
-        else                                                                                                       \
-            hipLaunchKernelGGL((dev::k_lp_scan_t<1, NW_>), gt, bt, lds_t, st, us, pairs, uoff, uids + y0, p_norm,    \
-                               norm_flag, global_E, ds, base, normal, rows);                                       \
-    }
-#define PT_LP(G_, V_, K_)                                                                                          \
-    if (s.G == G_ && s.VEC == V_ && s.KCH == K_) {                                                               \
-        for (int64_t y0 = 0; y0 < n_active; y0 += 65535) {                                                         \
-            const dim3 gs((unsigned)bx, (unsigned)(n_active - y0 < 65535 ? n_active - y0 : 65535));              \
-            if (y0 == 0) {                                                                                         \
-                if (model == 0)                                                                                    \
-                    hipLaunchKernelGGL((dev::k_lp_bases<0, G_, V_, K_>), gb, block, 0, st, us, pairs, n_pairs,    \
-                                       p_norm, norm_flag, ds, base, normal, tuple_min);                            \
-                else                                                                                               \
-                    hipLaunchKernelGGL((dev::k_lp_bases<1, G_, V_, K_>), gb, block, 0, st, us, pairs, n_pairs,    \
-                                       p_norm, norm_flag, ds, base, normal, tuple_min);                            \
-            }                                                                                                      \
-            if (PT_LP_SCAN_T && lds_t <= (160 << 10)) {                                                         \
-                const dim3 gt((unsigned)((max_ent + 63) / 64), gs.y), bt((unsigned)(64 * nw));                   \
-                PT_LPT(4) PT_LPT(8) PT_LPT(16)                                                                     \
-            } else if (model == 0)                                                                                 \
-                hipLaunchKernelGGL((dev::k_lp_scan<0, G_, V_, K_>), gs, block, 0, st, us, pairs, uoff, uids + y0,   \
-                                   p_norm, norm_flag, global_E, ds, base, normal, rows);                            \
-            else                                                                                                   \
-                hipLaunchKernelGGL((dev::k_lp_scan<1, G_, V_, K_>), gs, block, 0, st, us, pairs, uoff, uids + y0,   \
-                                   p_norm, norm_flag, global_E, ds, base, normal, rows);                            \
-        }                                                                                                          \
-        return hipGetLastError();                                                                                  \
-    }
-    PT_SHAPES(PT_LP)
-#undef PT_LP
-#undef PT_LPT
-    return hipErrorInvalidValue;
+    const dim3 gb((unsigned)((n_pairs + gpb - 1) / gpb)), block(256), bt(64 * kLpWaves);
+    hipError_t e = hipErrorInvalidValue;
+    for_shape(s, [&](auto sh) {
+        for_value<0, 1>(model != 0, [&](auto m) {
+            using T = decltype(sh);
+            const auto scan = dev::k_lp_scan_t<m.value, kLpWaves>;
+            if (lds_t > (64 << 10)) {
+                e = hipFuncSetAttribute(reinterpret_cast<const void *>(scan),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
+                if (e != hipSuccess) return;
+            }
+            for (int64_t y0 = 0; y0 < n_active; y0 += 65535) {   // (grid.y holds 65,535 universes)
+                if (y0 == 0)
+                    hipLaunchKernelGGL((dev::k_lp_bases<m.value, T::G, T::VEC, T::KCH>), gb, block, 0, st, us, pairs,
+                                       n_pairs, p_norm, norm_flag, ds, base, normal, tuple_min);
+                const dim3 gt((unsigned)((max_ent + 63) / 64), (unsigned)(n_active - y0 < 65535 ? n_active - y0 : 65535));
+                hipLaunchKernelGGL(scan, gt, bt, lds_t, st, us, pairs, uoff, uids + y0, p_norm, norm_flag, global_E, ds,
+                                   base, normal, rows);
+            }
+            e = hipGetLastError();
+        });
+    });
+    return e;
 }
 
 }  // namespace pt

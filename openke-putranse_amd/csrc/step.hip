@@ -1,10 +1,8 @@
 // HIP kernels of the training step (TransE / TransH forward + backward, gradient routing) for gfx950.
 //
 // Layout and mapping
-//  * Tables are row-major fp32 [rows][dim]. A "lane group" of G lanes (G | 64, a power of two) owns one
-//    row-sized vector: lane l holds chunks c = k*G + l (k < KCH) of VEC consecutive floats, so a row is
-//    read with fully coalesced 16-B (VEC=4) or 4-B (VEC=1) accesses and every reduction is a shuffle
-//    butterfly inside the group. One positive triple and all its negatives belong to one group.
+//  * Rows are held by lane groups (struct Shape, kernels.h). One positive triple and all its negatives
+//    belong to one group.
 //  * This is gather/axpy work (no dense contraction): the roofline is HBM / Infinity-Cache bandwidth
 //    and the memory-side float-atomic rate, not MFMA.
 //
@@ -571,21 +569,14 @@ int pick_nch(int64_t neg, int kch) {
     X(64, 1, 8, 1, 1) X(64, 1, 8, 4, 1) X(64, 1, 8, 8, 1) X(64, 1, 8, 8, 4)
 
 }  // namespace
-// k_step_csr instances (G, KCH, S), float4 lanes, chunks of kCsrNch rows
-#define PT_CSTEPS(X)                                                                 \
-    X(2, 1, 1) X(4, 1, 1) X(8, 1, 1) X(16, 1, 1) X(32, 1, 1) X(64, 1, 1)             \
-    X(2, 1, 2) X(4, 1, 2) X(8, 1, 2) X(16, 1, 2) X(32, 1, 2) X(64, 1, 2)             \
-    X(2, 1, 4) X(4, 1, 4) X(8, 1, 4) X(16, 1, 4) X(32, 1, 4) X(64, 1, 4)             \
-    X(64, 2, 1) X(64, 2, 2) X(64, 2, 4) X(64, 3, 1) X(64, 3, 4) X(64, 4, 1) X(64, 4, 4)
+// k_step_csr's instances are the VEC = 4 rows of PT_SHAPES x S in {1, 2, 4} x p_norm, with chunks of kCsrNch rows.
 // C2 (S = 4, 7 negatives per group): chunks of 2 rows, double-buffered, measured fastest
 static constexpr int kCsrNch = 2;
 
-// TransE on the counting-sort path with float4 rows takes k_step_csr; raw-buffer byte offsets must fit
-// in 31 bits
+// TransE on the counting-sort path with float4 rows takes k_step_csr (the contribution rows always count
+// towards the offsets' 31 bits)
 static bool csr_fast_path(const StepParams &P) {
-    const int64_t lim = int64_t(1) << 31;
-    const bool fits31 = (P.ent_total + P.rel_total + P.batch_size * P.neg) * P.dim * 4 < lim;
-    return P.model == 0 && P.dim % 4 == 0 && fits31;
+    return P.model == 0 && P.dim % 4 == 0 && offsets_fit31(P, P.batch_size * P.neg);
 }
 
 // whether launch_step can take this (P, neg) on the in-kernel-sampled path: k_step_csr has no LDS
@@ -607,46 +598,42 @@ hipError_t launch_step(const StepParams &P, const DeviceGraph &g, const uint64_t
                        float *loss, hipStream_t st, const CsrWork *csr) {
     if (P.batch_size <= 0) return hipSuccess;
     dev::GlobalSink sink{W.gent, W.grel, W.gnorm, W.fent, W.frel, W.fnorm, W.lpart};
+    hipError_t e = hipErrorInvalidValue;
     if (bh) {   // external batch
         const Shape s = pick_shape(P.dim);
         const int64_t gpb = 256 / s.G;
         const dim3 grid((unsigned)((P.batch_size + gpb - 1) / gpb)), block(256);
-#define PT_STEP(G_, V_, K_)                                                                                        \
-        if (s.G == G_ && s.VEC == V_ && s.KCH == K_) {                                                           \
-            if (P.model == 0)                                                                                      \
-                hipLaunchKernelGGL((dev::k_step<0, G_, V_, K_>), grid, block, 0, st, P, bh, bt, br, sink, loss);   \
-            else                                                                                                   \
-                hipLaunchKernelGGL((dev::k_step<1, G_, V_, K_>), grid, block, 0, st, P, bh, bt, br, sink, loss);   \
-            return hipGetLastError();                                                                              \
-        }
-        PT_SHAPES(PT_STEP)
-#undef PT_STEP
-        return hipErrorInvalidValue;
+        for_shape(s, [&](auto sh) {
+            for_value<0, 1>(P.model != 0, [&](auto m) {
+                using T = decltype(sh);
+                hipLaunchKernelGGL((dev::k_step<m.value, T::G, T::VEC, T::KCH>), grid, block, 0, st, P, bh, bt, br, sink,
+                                   loss);
+                e = hipGetLastError();
+            });
+        });
+        return e;
     }
     // TransE on a counting-sort batch with float4 rows: k_step_csr (S lane groups per positive)
     if (csr && csr_fast_path(P)) {
-        const int64_t chunks = P.dim / 4;
-        int G = 2;
-        while (G < chunks && G < 64) G <<= 1;
-        const int KCH = (int)((chunks + G - 1) / G);
+        const Shape s = pick_shape(P.dim);
         // split a positive's negatives over S lane groups of one block (more waves in flight: the step
         // is latency-bound when one group walks all negatives)
         int S = 1;
-        while (S < 4 && S * 2 <= 256 / G && P.neg >= 6 * S * 2) S *= 2;
-#define PT_CSTEP(G_, K_, S_)                                                                           \
-        if (G == G_ && KCH == K_ && S == S_) {                                                       \
-            constexpr int NT_ = S_ * G_ >= 256 || 256 % (S_ * G_) != 0 ? S_ * G_ : 256;             \
-            const dim3 grid((unsigned)((P.batch_size * S_ * G_ + NT_ - 1) / NT_)), block(NT_);        \
-            if (P.p_norm == 1)                                                                       \
-                hipLaunchKernelGGL((dev::k_step_csr<G_, 4, K_, kCsrNch, S_, 1, NT_>), grid, block, 0, st, P, sink, \
-                                   *csr);                                                              \
-            else                                                                                     \
-                hipLaunchKernelGGL((dev::k_step_csr<G_, 4, K_, kCsrNch, S_, 2, NT_>), grid, block, 0, st, P, sink, \
-                                   *csr);                                                              \
-            return hipGetLastError();                                                                \
-        }
-        PT_CSTEPS(PT_CSTEP)
-#undef PT_CSTEP
+        while (S < 4 && S * 2 <= 256 / s.G && P.neg >= 6 * S * 2) S *= 2;
+        const bool matched = for_shape(s, [&](auto sh) {
+            using T = decltype(sh);
+            if constexpr (T::VEC == 4)
+                for_value<1, 2, 4>(S, [&](auto sv) {
+                    for_value<1, 2>(P.p_norm == 1 ? 1 : 2, [&](auto pn) {
+                        constexpr int SG = sv.value * T::G, NT = SG >= 256 || 256 % SG != 0 ? SG : 256;
+                        const dim3 grid((unsigned)((P.batch_size * SG + NT - 1) / NT)), block(NT);
+                        hipLaunchKernelGGL((dev::k_step_csr<T::G, 4, T::KCH, kCsrNch, sv.value, pn.value, NT>), grid,
+                                           block, 0, st, P, sink, *csr);
+                        e = hipGetLastError();
+                    });
+                });
+        });
+        if (matched) return e;
     }
     // row layout: one float per lane (each wave instruction moves 64 contiguous floats)
     {
@@ -662,23 +649,14 @@ hipError_t launch_step(const StepParams &P, const DeviceGraph &g, const uint64_t
         if (lds > 64 * 1024) return hipErrorInvalidValue;
         const CsrWork cw = csr ? *csr : CsrWork{};
 #define PT_SSTEP(G_, V_, K_, N_, S_)                                                                                 \
-        if (s.G == G_ && s.VEC == V_ && s.KCH == K_ && nch == N_ && S == S_) {                                           \
-            if (csr) {                                                                                            \
-                if (P.model == 0)                                                                                 \
-                    hipLaunchKernelGGL((dev::k_step_sampled<0, G_, V_, K_, N_, S_, true>), grid, block, lds, st,        \
-                                       P, g, states, threads, bern, filter, sink, loss, cw);                      \
-                else                                                                                              \
-                    hipLaunchKernelGGL((dev::k_step_sampled<1, G_, V_, K_, N_, S_, true>), grid, block, lds, st,        \
-                                       P, g, states, threads, bern, filter, sink, loss, cw);                      \
-            } else {                                                                                              \
-                if (P.model == 0)                                                                                 \
-                    hipLaunchKernelGGL((dev::k_step_sampled<0, G_, V_, K_, N_, S_, false>), grid, block, lds, st,       \
-                                       P, g, states, threads, bern, filter, sink, loss, cw);                      \
-                else                                                                                              \
-                    hipLaunchKernelGGL((dev::k_step_sampled<1, G_, V_, K_, N_, S_, false>), grid, block, lds, st,       \
-                                       P, g, states, threads, bern, filter, sink, loss, cw);                      \
-            }                                                                                                     \
-            return hipGetLastError();                                                                             \
+        if (s.G == G_ && s.VEC == V_ && s.KCH == K_ && nch == N_ && S == S_) {                                       \
+            for_value<0, 1>(P.model != 0, [&](auto m) {                                                              \
+                for_value<0, 1>(csr != nullptr, [&](auto c) {                                                        \
+                    hipLaunchKernelGGL((dev::k_step_sampled<m.value, G_, V_, K_, N_, S_, c.value != 0>), grid, block, \
+                                       lds, st, P, g, states, threads, bern, filter, sink, loss, cw);                \
+                });                                                                                                  \
+            });                                                                                                      \
+            return hipGetLastError();                                                                                \
         }
         // the preferred chunk size first, then any instantiated one (the kernel loops over chunks)
         const int cands[5] = {nch, 8, 4, 32, 1};

@@ -332,32 +332,31 @@ hipError_t launch_step_adv(const StepParams &P, const LossParams &L, const int64
             const int64_t g2 = std::min<int64_t>(256 / s.G, lim / per);
             const dim3 grid2((unsigned)((P.batch_size + g2 - 1) / g2)), block2((unsigned)(g2 * s.G));
             const size_t lds2 = sizeof(float) * (size_t)(g2 * per);
-#define PT_ADVS(G_, V_, K_)                                                                                     \
-            if (s.G == G_ && s.KCH == K_) {                                                                    \
-                auto kern = dev::k_step_adv<G_, 4, K_, 4, true>;                                               \
-                hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                   (int)lds2);                                                 \
-                if (e != hipSuccess) return e;                                                                 \
-                hipLaunchKernelGGL(kern, grid2, block2, lds2, st, P, L, bh, bt, br, sink, W.lpart);            \
-                return hipGetLastError();                                                                      \
-            }
-            PT_ADVS(2, 4, 1) PT_ADVS(4, 4, 1) PT_ADVS(8, 4, 1) PT_ADVS(16, 4, 1) PT_ADVS(32, 4, 1) PT_ADVS(64, 4, 1)
-            PT_ADVS(64, 4, 2)
-#undef PT_ADVS
+            hipError_t e = hipErrorInvalidValue;
+            const bool staged = for_shape(s, [&](auto sh) {
+                using T = decltype(sh);
+                if constexpr (T::VEC == 4) {
+                    auto kern = dev::k_step_adv<T::G, 4, T::KCH, 4, true>;
+                    e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+                    if (e != hipSuccess) return;
+                    hipLaunchKernelGGL(kern, grid2, block2, lds2, st, P, L, bh, bt, br, sink, W.lpart);
+                    e = hipGetLastError();
+                }
+            });
+            if (staged) return e;
         }
     }
 #endif
     const dim3 grid((unsigned)((P.batch_size + gpb - 1) / gpb)), block((unsigned)(gpb * s.G));
     const size_t lds = sizeof(float) * (size_t)(gpb * (P.neg + rw));
-#define PT_ADV(G_, V_, K_)                                                                                      \
-    if (s.G == G_ && s.VEC == V_ && s.KCH == K_) {                                                             \
-        hipLaunchKernelGGL((dev::k_step_adv<G_, V_, K_, 4>), grid, block, lds, st, P, L, bh, bt, br, sink,    \
-                           W.lpart);                                                                           \
-        return hipGetLastError();                                                                              \
-    }
-    PT_SHAPES(PT_ADV)
-#undef PT_ADV
-    return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;
+    for_shape(s, [&](auto sh) {
+        using T = decltype(sh);
+        hipLaunchKernelGGL((dev::k_step_adv<T::G, T::VEC, T::KCH, 4>), grid, block, lds, st, P, L, bh, bt, br, sink,
+                           W.lpart);
+        e = hipGetLastError();
+    });
+    return e;
 }
 
 }  // namespace pt

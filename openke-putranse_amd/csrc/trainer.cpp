@@ -350,16 +350,22 @@ static int join_sample_split(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t n
     return PT_OK;
 }
 
+// the trainer's step parameters for batches of bs positives x neg negatives
+static pt::StepParams batch_params(const pt_trainer *t, int64_t bs, int64_t neg) {
+    pt::StepParams P = t->P;
+    P.batch_size = bs;
+    P.neg = neg;
+    P.inv_count = 1.0f / (float)(bs * neg);
+    return P;
+}
+
 // Enqueue `steps` in-kernel-sampled steps; step i adds its loss to d_losses[i]. Large neg takes the
 // counting-sort path: one sampling + one scan launch per chunk of up to kCsrChunk steps (the batch
 // stream does not depend on the tables, so it is drawn ahead), then k_step + k_apply per step.
 static int enqueue_run(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, int64_t bern, int64_t filter,
                        int64_t steps, float *d_losses, hipStream_t st, Timing *tm = nullptr, bool assign = false) {
-    pt::StepParams P = t->P;
+    pt::StepParams P = batch_params(t, bs, neg);
     P.loss_assign = assign ? 1 : 0;   // d_losses[i] = step i's loss (no zeroing pass needed)
-    P.batch_size = bs;
-    P.neg = neg;
-    P.inv_count = 1.0f / (float)(bs * neg);
     const int64_t dpp = 1 + 2 * neg;
     const pt::DeviceGraph dg = s->g->dev;
     if (use_csr(neg)) {
@@ -395,10 +401,7 @@ static int enqueue_run(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, in
 // (ev: optional three events recorded before the step kernel, between the two kernels and after the apply kernel)
 static int enqueue_external(pt_trainer *t, int64_t bs, int64_t neg, const int64_t *bh, const int64_t *bt,
                             const int64_t *br, float *d_loss, hipStream_t st, hipEvent_t *ev = nullptr) {
-    pt::StepParams P = t->P;
-    P.batch_size = bs;
-    P.neg = neg;
-    P.inv_count = 1.0f / (float)(bs * neg);
+    pt::StepParams P = batch_params(t, bs, neg);
     const bool adam = P.opt == PT_ADAM;
     PT_CHECK(!adam || t->adam_set, PT_ESTATE, "PT_ADAM needs pt_trainer_set_adam before the first step");
     float scale = P.inv_count, cst = P.margin;   // loss = scale * sum(lpart) + cst
@@ -702,10 +705,7 @@ extern "C" int pt_trainer_run_timed(pt_trainer *t, pt_sampler *s, int64_t bs, in
     //   loop 1: `steps` x (forward/backward, apply)  -> T_sa;   loop 2: `steps` x forward/backward -> T_s
     // ms4[2] = T_s / steps, ms4[3] = (T_sa - T_s) / steps. The tables, Adagrad state, gradient rows and
     // flags are restored afterwards, so training state is exactly as the measured run left it.
-    pt::StepParams P = t->P;
-    P.batch_size = bs;
-    P.neg = neg;
-    P.inv_count = 1.0f / (float)(bs * neg);
+    pt::StepParams P = batch_params(t, bs, neg);
     const int64_t E = P.ent_total, R = P.rel_total, D = P.dim, dpp = 1 + 2 * neg;
     std::vector<std::pair<float *, size_t>> keep = {{P.ent, 4 * E * D}, {P.rel, 4 * R * D}};
     if (P.normv) keep.push_back({P.normv, 4 * R * D});

@@ -35,31 +35,31 @@ int universe_shape_id(int64_t D, int model) {
 
 bool universe_shape_supported(int64_t D, int model) { return universe_shape_id(D, model) >= 0; }
 
+// the row shape of a shape id
+static bool universe_shape(int shape, Shape *s) {
+#define PT_UROW(ID_, G_, V_, K_) \
+    if (shape == ID_) return *s = Shape{G_, V_, K_}, true;
+    PT_USHAPES(PT_UROW)
+#undef PT_UROW
+    return false;
+}
+
 // shape class of a row shape (one kernel per class)
 int universe_shape_class(int shape) {
-#define PT_UCLS(ID_, G_, V_, K_) \
-    if (shape == ID_) return PT_UCLASS(V_, K_);
-    PT_USHAPES(PT_UCLS)
-#undef PT_UCLS
-    return 1;
+    Shape s{};
+    return universe_shape(shape, &s) ? PT_UCLASS(s.VEC, s.KCH) : 1;
 }
 
 // lane groups of a universe workgroup for a shape (positives of a step processed concurrently)
 int universe_shape_groups(int shape, int model) {
-#define PT_UGPB(ID_, G_, V_, K_) \
-    if (shape == ID_) return universe_class_threads(model, PT_UCLASS(V_, K_)) / G_;
-    PT_USHAPES(PT_UGPB)
-#undef PT_UGPB
-    return 1;
+    Shape s{};
+    return universe_shape(shape, &s) ? universe_class_threads(model, PT_UCLASS(s.VEC, s.KCH)) / s.G : 1;
 }
 
 // padded row length of a row shape (lanes x floats per lane: the floats a lane group touches per row)
 int universe_shape_row_slots(int shape) {
-#define PT_URS(ID_, G_, V_, K_) \
-    if (shape == ID_) return G_ * V_ * K_;
-    PT_USHAPES(PT_URS)
-#undef PT_URS
-    return 1;
+    Shape s{};
+    return universe_shape(shape, &s) ? s.G * s.VEC * s.KCH : 1;
 }
 
 // the LDS plan the launch configuration amounts to (universe_run's PLAN): 1 and 2 are compiled apart with

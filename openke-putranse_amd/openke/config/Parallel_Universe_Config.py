@@ -1059,7 +1059,7 @@ class Parallel_Universe_Config(Tester):
 
     # ------------------------------------------- the reference's per-(key, universe) internals ----
     # eval_universes scores every (key, universe) pair of a split in two GPU launches into device key rows
-    # (k_lp_bases / k_lp_scan). These are the reference's one-pair steps (:446-543), kept for callers that
+    # (k_lp_bases / k_lp_scan_t). These are the reference's one-pair steps (:446-543), kept for callers that
     # drive them directly: the universe's scores come from one GPU predict, and the MIN goes into the
     # reference's score dictionaries (rows of entTotal floats, +inf default), which
     # global_energy_estimation reads together with the device rows.
