@@ -77,11 +77,15 @@ int pt_sampler_sample_ex(pt_sampler *s, int64_t bs, int64_t neg, int64_t neg_rel
                          int64_t filter, int64_t *d_h, int64_t *d_t, int64_t *d_r, float *d_y, void *stream);
 
 /* ------------------------------------------------------------------ training ---------------- */
-enum { PT_TRANSE = 0, PT_TRANSH = 1 };
+/* PT_TRANSD (TransD.py with dim_e == dim_r): one model through pt_trainer_* on external batches (plain MarginLoss;
+ * SGD, Adagrad, Adam) and pt_score / pt_score_queries / pt_score_rows. In-kernel sampling, captured runs
+ * (pt_trainer_run, pt_trainer_run_timed), the reference-order mode, any other loss and every universe entry point
+ * (pt_universes_train*, pt_universe_set_create, pt_universe_dim_supported, pt_lp_min_scores) refuse it. */
+enum { PT_TRANSE = 0, PT_TRANSH = 1, PT_TRANSD = 2 };
 enum { PT_SGD = 0, PT_ADAGRAD = 1, PT_ADAM = 2 };
 
 typedef struct {
-    int32_t model;        /* PT_TRANSE | PT_TRANSH */
+    int32_t model;        /* PT_TRANSE | PT_TRANSH | PT_TRANSD */
     int32_t p_norm;       /* 1 or 2  (TransE.py:46-60) */
     int32_t norm_flag;    /* F.normalize of h, r, t before scoring */
     int32_t opt;          /* PT_SGD | PT_ADAGRAD (Trainer.py:62-88; eps 1e-10, lr_decay 0) | PT_ADAM (state:
@@ -91,6 +95,9 @@ typedef struct {
     int64_t ent_total, rel_total, dim;
     float *ent, *rel, *normv;              /* device tables [rows][dim], row-major fp32 */
     float *ent_acc, *rel_acc, *norm_acc;   /* Adagrad state_sum (NULL for SGD) */
+    /* PT_TRANSD only (NULL otherwise): ent_transfer [ent_total][dim], rel_transfer [rel_total][dim] and their
+     * Adagrad state_sum. Appended: a caller that zero-initialises the struct and fills the fields above is unchanged. */
+    float *ent_transfer, *rel_transfer, *ent_transfer_acc, *rel_transfer_acc;
 } pt_model_desc;
 
 /* Workspace for minibatch-synchronous steps on one model (gradient rows, touched-row flags). */
@@ -151,18 +158,22 @@ int pt_trainer_set_loss(pt_trainer *t, const pt_loss_desc *loss);
  * exp_avg / exp_avg_sq shaped like the tables (norm_* NULL for TransE), the betas, eps and the number of steps
  * already done. Adam is dense: every step updates every row of every table (k_apply_adam). The trainer counts the
  * steps from `step` on (pt_trainer_adam_step reads the count; -1 for a null trainer); the tables share the count.
- * Adam trains external batches only (PT_ENOTSUP otherwise, as for pt_trainer_set_loss), TransE and TransH. */
+ * Adam trains external batches only (PT_ENOTSUP otherwise, as for pt_trainer_set_loss), TransE, TransH and TransD
+ * (whose two transfer tables take a second k_apply_adam launch). */
 typedef struct {
     float *ent_m, *rel_m, *norm_m;   /* exp_avg */
     float *ent_v, *rel_v, *norm_v;   /* exp_avg_sq */
     double beta1, beta2, eps;        /* doubles: 1 - beta is formed in double, as torch forms it */
     int64_t step;
+    /* PT_TRANSD only (NULL otherwise): the moments of ent_transfer and rel_transfer */
+    float *ent_transfer_m, *rel_transfer_m, *ent_transfer_v, *rel_transfer_v;
 } pt_adam_state;
 int pt_trainer_set_adam(pt_trainer *t, const pt_adam_state *state);
 int64_t pt_trainer_adam_step(const pt_trainer *t);
 /* Measurement hook of the external-batch step (tools/bench_adv.py): `steps` steps on ONE device batch (layout of
  * pt_trainer_step), launched one by one with events around both launches of every step. ms2[0] = mean duration of
- * the step kernel (k_step / k_step_adv), ms2[1] = of the apply kernel (k_apply / k_apply_adam). The steps train:
+ * the step kernel (k_step / k_step_adv / k_step_transd), ms2[1] = of the apply kernel (k_apply / k_apply_adam; both
+ * launches of it for PT_TRANSD). The steps train:
  * tables, optimizer state and the Adam step count advance, *d_loss accumulates. Synchronizes the stream. */
 int pt_trainer_steps_timed(pt_trainer *t, int64_t bs, int64_t neg, const int64_t *d_batch_h, const int64_t *d_batch_t,
                            const int64_t *d_batch_r, int64_t steps, float *d_loss, float *ms2, void *stream);
@@ -205,7 +216,7 @@ int pt_trainer_sample_csr(pt_trainer *t, pt_sampler *sampler, int64_t bs, int64_
                           int32_t *h_start, void *stream);
 
 /* ------------------------------------------------------------------ scoring ------------------ */
-/* scores = ||h + r - t||_p as model.predict computes them (TransE.py:46-74, TransH.py:52-93):
+/* scores = ||h + r - t||_p as model.predict computes them (TransE.py:46-74, TransH.py:52-93, TransD.py:94-129):
  * mode 0 normal (all three arrays length n), 1 head_batch (d_h length n, t and r length 1),
  * 2 tail_batch (d_t length n, h and r length 1). */
 int pt_score(const pt_model_desc *m, int32_t mode, const int64_t *d_h, const int64_t *d_t, const int64_t *d_r,

@@ -41,15 +41,19 @@ extern "C" int pt_version(void) { return 1; }
 // ======================================================================== model descriptor =======
 int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
     PT_CHECK(m, PT_EINVAL, "null model descriptor");
-    PT_CHECK(m->model == PT_TRANSE || m->model == PT_TRANSH, PT_EINVAL, "model must be PT_TRANSE or PT_TRANSH");
+    PT_CHECK(m->model == PT_TRANSE || m->model == PT_TRANSH || m->model == PT_TRANSD, PT_EINVAL,
+             "model must be PT_TRANSE, PT_TRANSH or PT_TRANSD");
     PT_CHECK(m->p_norm == 1 || m->p_norm == 2, PT_ENOTSUP, "p_norm must be 1 or 2");
     PT_CHECK(m->opt == PT_SGD || m->opt == PT_ADAGRAD || m->opt == PT_ADAM, PT_EINVAL,
              "opt must be PT_SGD, PT_ADAGRAD or PT_ADAM");
     PT_CHECK(pt::shape_supported(m->dim), PT_ENOTSUP, "embedding dim " + std::to_string(m->dim) + " not supported");
     PT_CHECK(m->ent && m->rel && m->ent_total > 0 && m->rel_total > 0, PT_EINVAL, "missing tables");
-    PT_CHECK(m->model == PT_TRANSE || m->normv, PT_EINVAL, "TransH needs norm_vector");
-    PT_CHECK(m->opt != PT_ADAGRAD || (m->ent_acc && m->rel_acc && (m->model == PT_TRANSE || m->norm_acc)), PT_EINVAL,
-             "Adagrad needs state_sum buffers");
+    PT_CHECK(m->model != PT_TRANSH || m->normv, PT_EINVAL, "TransH needs norm_vector");
+    PT_CHECK(m->model != PT_TRANSD || (m->ent_transfer && m->rel_transfer), PT_EINVAL,
+             "TransD needs ent_transfer and rel_transfer");
+    PT_CHECK(m->opt != PT_ADAGRAD || (m->ent_acc && m->rel_acc && (m->model != PT_TRANSH || m->norm_acc) &&
+                                      (m->model != PT_TRANSD || (m->ent_transfer_acc && m->rel_transfer_acc))),
+             PT_EINVAL, "Adagrad needs state_sum buffers");
     P.model = m->model;
     P.p_norm = m->p_norm;
     P.norm_flag = m->norm_flag ? 1 : 0;
@@ -61,6 +65,10 @@ int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
     P.dim = m->dim;
     P.ent = m->ent; P.rel = m->rel; P.normv = m->normv;
     P.ent_acc = m->ent_acc; P.rel_acc = m->rel_acc; P.norm_acc = m->norm_acc;
+    if (m->model == PT_TRANSD) {
+        P.ent_t = m->ent_transfer; P.rel_t = m->rel_transfer;
+        P.ent_t_acc = m->ent_transfer_acc; P.rel_t_acc = m->rel_transfer_acc;
+    }
     if (const char *v = pt_tuning_env("PT_STEP_DBG")) P.dbg = atoi(v);
     return PT_OK;
 }
@@ -329,6 +337,7 @@ extern "C" int64_t pt_lp_keys_per_batch(int64_t global_ent_total) { return lp_ke
 extern "C" int pt_lp_min_scores(const pt_lp_universe *us, int64_t n_universes, int32_t model, int32_t p_norm,
                                 int32_t norm_flag, const pt_lp_pair *pairs, int64_t n_pairs,
                                 int64_t global_ent_total, float *d_key_rows, float *d_key_tuple, void *stream) {
+    PT_CHECK(model != PT_TRANSD, PT_ENOTSUP, "pt_lp_min_scores: PuTransD universes are not built yet (PT_TRANSD)");
     PT_CHECK((us && pairs && d_key_rows) || n_pairs == 0, PT_EINVAL, "pt_lp_min_scores: null argument");
     if (n_pairs == 0) return PT_OK;
     hipStream_t st = (hipStream_t)stream;

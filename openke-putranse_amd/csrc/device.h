@@ -112,6 +112,33 @@ __device__ __forceinline__ void vatomic(const V<G, VEC, KCH> &o, float *__restri
     }
 }
 
+// Float atomics of a row vector into a gradient row (k_step_adv, k_step_transd). float4 lanes would make one atomic
+// wave-instruction touch floats 16 B apart (4x the cache lines): the vector passes through the group's LDS row `tb`
+// (KCH * G * 4 floats) instead, so lane l adds floats l, l + G, ... (256 contiguous bytes per instruction at G = 64),
+// as k_step_csr does for the positive's rows (measured: DESIGN.md section 4). The group is inside one wave, whose LDS
+// accesses execute in program order.
+template <int G, int VEC, int KCH>
+__device__ __forceinline__ void row_atomic(const V<G, VEC, KCH> &g, float *__restrict__ row, float *tb, int D,
+                                           int lane) {
+    if constexpr (VEC == 1) {
+        vatomic(g, row, D, lane);
+    } else {
+#pragma unroll
+        for (int k = 0; k < KCH; ++k) {
+            const int c = k * G + lane;
+            *reinterpret_cast<float4 *>(tb + c * 4) =
+                make_float4(g.x[k * 4 + 0], g.x[k * 4 + 1], g.x[k * 4 + 2], g.x[k * 4 + 3]);
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int j = 0; j < KCH * VEC; ++j) {
+            const int c = j * G + lane;
+            if (c < D) atomicAdd(row + c, tb[c]);
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // Address-space-typed pointers: rows reached through pointers loaded from memory (a universe descriptor)
 // or selected at run time between LDS and HBM are generic ("flat") to the compiler, and a flat access
 // counts in BOTH vmcnt and lgkmcnt - every LDS wait then also waits for the in-flight HBM loads. Kernels

@@ -20,6 +20,10 @@ struct StepParams {
     int loss_assign = 0;   // the apply pass stores the step's loss (=) instead of adding it (+=)
     int dbg = 0;       // timing experiments only (PT_STEP_DBG): bit 0 skip corrupted-row stores, bit 1 skip
                        // positive-row atomics, bit 2 skip negative row loads (results are then wrong)
+    // TransD (model 2): ent_transfer / rel_transfer and their Adagrad state (appended: the fields above keep their
+    // places in the argument blocks of the TransE / TransH kernels)
+    float *ent_t = nullptr, *rel_t = nullptr;
+    float *ent_t_acc = nullptr, *rel_t_acc = nullptr;
 };
 
 struct StepWorkspace {
@@ -29,6 +33,9 @@ struct StepWorkspace {
     // pass reduces them in a fixed order into the step's loss (one same-address float atomic per
     // positive serialises at the memory side: it cost ~13 us per C2 step)
     float *lpart = nullptr;
+    // TransD: gradient rows and touched flags of ent_transfer / rel_transfer
+    float *gentt = nullptr, *grelt = nullptr;
+    int *fentt = nullptr, *frelt = nullptr;
 };
 
 // Workspace of the counting-sort (CSR) gradient path for large neg (see k_sample_csr). The sampling
@@ -181,7 +188,8 @@ inline void loss_affine(const LossParams &L, const StepParams &P, float *scale, 
 }
 // dense Adam (adam.hip; pt_adam_state): m / v per table, the step's bias corrections computed on the host in double
 struct AdamParams {
-    float *m[3] = {nullptr, nullptr, nullptr}, *v[3] = {nullptr, nullptr, nullptr};
+    // tables 0-2: ent, rel, norm_vector; 3-4: TransD's ent_transfer, rel_transfer
+    float *m[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     double beta1 = 0.9, beta2 = 0.999, eps = 1e-8;   // (1 - beta in double: 1.0f - 0.999f is 1.3e-5 off 0.001)
     float step_size = 0.f;   // lr / (1 - beta1^t)
     float bc2_sqrt = 1.f;    // sqrt(1 - beta2^t)
@@ -194,6 +202,28 @@ hipError_t launch_step_adv(const StepParams &P, const LossParams &L, const int64
 // loss partials: loss (+)= loss_scale * sum(lpart) + loss_cst
 hipError_t launch_apply_adam(const StepParams &P, const StepWorkspace &W, const AdamParams &A, int64_t bs,
                              float loss_scale, float loss_cst, float *loss, hipStream_t st);
+// TransD (transd.hip): the external-batch step under plain MarginLoss (entity and transfer gradients finished in the
+// kernel, the relation's left in normalised space), and the scores; launch_score / launch_score_queries route model 2
+// to the latter two. The optimizer pass runs twice for TransD: (ent, rel), then transd_transfer_pass's view
+hipError_t launch_step_transd(const StepParams &P, const int64_t *bh, const int64_t *bt, const int64_t *br,
+                              const StepWorkspace &W, hipStream_t st);
+hipError_t launch_score_transd(const StepParams &P, int mode, const int64_t *h, const int64_t *t, const int64_t *r,
+                               int64_t n, float *out, hipStream_t st);
+hipError_t launch_score_queries_transd(const StepParams &P, int side, const int64_t *qh, const int64_t *qt,
+                                       const int64_t *qr, int64_t nq, int64_t E, float *out, hipStream_t st,
+                                       int global_order);
+// the (ent_transfer, rel_transfer) pair of a TransD step seen as the (ent, rel) pair of a second optimizer pass: no
+// Jacobian (the step kernel finished both gradients), no loss partials (the first pass reduced them)
+inline void transd_transfer_pass(const StepParams &P, const StepWorkspace &W, StepParams *P2, StepWorkspace *W2) {
+    *P2 = P;
+    P2->ent = P.ent_t; P2->rel = P.rel_t;
+    P2->ent_acc = P.ent_t_acc; P2->rel_acc = P.rel_t_acc;
+    P2->norm_flag = 0;
+    *W2 = W;
+    W2->gent = W.gentt; W2->grel = W.grelt;
+    W2->fent = W.fentt; W2->frel = W.frelt;
+    W2->lpart = nullptr;
+}
 hipError_t launch_score(const StepParams &P, int mode, const int64_t *h, const int64_t *t, const int64_t *r, int64_t n,
                         float *out, hipStream_t st);
 hipError_t launch_score_queries(const StepParams &P, int side, const int64_t *qh, const int64_t *qt, const int64_t *qr,

@@ -1073,6 +1073,7 @@ hipError_t launch_scan_counts(const CsrWork &w, int64_t n, int64_t calls, uint64
 hipError_t launch_score(const StepParams &P, int mode, const int64_t *h, const int64_t *t, const int64_t *r, int64_t n,
                         float *out, hipStream_t st) {
     if (n <= 0) return hipSuccess;
+    if (P.model == 2) return launch_score_transd(P, mode, h, t, r, n, out, st);
     const Shape s = pick_shape(P.dim);
     const int64_t gpb = 256 / s.G;
     const dim3 grid((unsigned)((n + gpb - 1) / gpb)), block(256);
@@ -1091,6 +1092,7 @@ hipError_t launch_score(const StepParams &P, int mode, const int64_t *h, const i
 hipError_t launch_score_queries(const StepParams &P, int side, const int64_t *qh, const int64_t *qt, const int64_t *qr,
                                 int64_t nq, int64_t E, float *out, hipStream_t st, int global_order) {
     if (nq <= 0) return hipSuccess;
+    if (P.model == 2) return launch_score_queries_transd(P, side, qh, qt, qr, nq, E, out, st, global_order);
     const Shape s = pick_shape(P.dim);
     const int64_t gpb = 256 / s.G;
     int64_t bx = (E + gpb - 1) / gpb;

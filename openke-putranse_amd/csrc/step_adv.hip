@@ -48,33 +48,7 @@ __device__ __forceinline__ float sigm(float x) {
     return (x >= 0.f ? 1.0f : e) / (1.0f + e);
 }
 
-// Float atomics of a row vector into a gradient row. float4 lanes would make one atomic wave-instruction touch
-// floats 16 B apart (4x the cache lines): the vector passes through the group's LDS row `tb` instead, so lane l adds
-// floats l, l + G, ... (256 contiguous bytes per instruction at G = 64), as k_step_csr does for the positive's rows
-// (measured here: DESIGN.md section 4). The group is inside one wave, whose LDS accesses execute in program order.
-template <int G, int VEC, int KCH>
-__device__ __forceinline__ void row_atomic(const V<G, VEC, KCH> &g, float *__restrict__ row, float *tb, int D,
-                                           int lane) {
-    if constexpr (VEC == 1) {
-        vatomic(g, row, D, lane);
-    } else {
-#pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int c = k * G + lane;
-            *reinterpret_cast<float4 *>(tb + c * 4) =
-                make_float4(g.x[k * 4 + 0], g.x[k * 4 + 1], g.x[k * 4 + 2], g.x[k * 4 + 3]);
-        }
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int j = 0; j < KCH * VEC; ++j) {
-            const int c = j * G + lane;
-            if (c < D) atomicAdd(row + c, tb[c]);
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-struct AdvSink {
+struct AdvSink {   // (row_atomic: device.h)
     float *gent, *grel;
     int *fent, *frel;
     template <int G, int VEC, int KCH>

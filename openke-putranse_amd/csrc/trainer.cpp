@@ -65,7 +65,7 @@ struct pt_trainer {
     bool adam_set = false;
     int64_t adam_step = 0;   // steps done
     // anything the in-kernel-sampled, captured and reference-order paths do not compute
-    bool extended() const { return !loss.plain() || P.opt == PT_ADAM; }
+    bool extended() const { return !loss.plain() || P.opt == PT_ADAM || P.model == PT_TRANSD; }
     void drop_graphs() {
         for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
         graphs.clear();
@@ -120,7 +120,9 @@ extern "C" int pt_trainer_create(const pt_model_desc *m, pt_trainer **out) {
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t ge = al(4 * E * D), gr = al(4 * R * D), gn = m->model == PT_TRANSH ? al(4 * R * D) : 0;
     const size_t fe = al(4 * E), fr = al(4 * R), fn = m->model == PT_TRANSH ? al(4 * R) : 0;
-    const size_t total = ge + gr + gn + fe + fr + fn;
+    // TransD: gradient rows and flags of ent_transfer / rel_transfer, shaped like ent / rel
+    const bool td = m->model == PT_TRANSD;
+    const size_t total = ge + gr + gn + fe + fr + fn + (td ? ge + gr + fe + fr : 0);
     PT_HIP(hipMalloc(&t->ws_block, total));
     PT_HIP(hipMemset(t->ws_block, 0, total));
     t->ws_bytes = total;
@@ -130,7 +132,13 @@ extern "C" int pt_trainer_create(const pt_model_desc *m, pt_trainer **out) {
     t->W.gnorm = gn ? (float *)b : nullptr; b += gn;
     t->W.fent = (int *)b; b += fe;
     t->W.frel = (int *)b; b += fr;
-    t->W.fnorm = fn ? (int *)b : nullptr;
+    t->W.fnorm = fn ? (int *)b : nullptr; b += fn;
+    if (td) {
+        t->W.gentt = (float *)b; b += ge;
+        t->W.grelt = (float *)b; b += gr;
+        t->W.fentt = (int *)b; b += fe;
+        t->W.frelt = (int *)b;
+    }
     PT_HIP(hipStreamCreateWithFlags(&t->cap, hipStreamNonBlocking));
     PT_HIP(hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking));
     PT_HIP(hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming));
@@ -406,7 +414,12 @@ static int enqueue_external(pt_trainer *t, int64_t bs, int64_t neg, const int64_
     PT_CHECK(!adam || t->adam_set, PT_ESTATE, "PT_ADAM needs pt_trainer_set_adam before the first step");
     float scale = P.inv_count, cst = P.margin;   // loss = scale * sum(lpart) + cst
     if (ev) PT_HIP(hipEventRecord(ev[0], st));
-    if (t->loss.plain()) {
+    const bool transd = P.model == PT_TRANSD;
+    if (transd) {
+        PT_CHECK(t->loss.plain(), PT_ENOTSUP,
+                 "SigmoidLoss, adversarial weights and a model margin train TransE only (TransD is not implemented)");
+        PT_HIP(pt::launch_step_transd(P, bh, bt, br, t->W, st));
+    } else if (t->loss.plain()) {
         PT_HIP(pt::launch_step(P, pt::DeviceGraph{}, nullptr, 0, 0, 0, bh, bt, br, t->W, d_loss, st));
     } else {
         PT_CHECK(P.model == PT_TRANSE, PT_ENOTSUP,
@@ -424,19 +437,34 @@ static int enqueue_external(pt_trainer *t, int64_t bs, int64_t neg, const int64_
         A.step_size = (float)((double)P.lr / (1.0 - std::pow(A.beta1, step)));
         A.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(A.beta2, step));
         PT_HIP(pt::launch_apply_adam(P, t->W, A, bs, scale, cst, d_loss, st));
+        if (transd) {   // the two transfer tables: a second pass with no loss (transd_transfer_pass)
+            pt::StepParams P2;
+            pt::StepWorkspace W2;
+            pt::transd_transfer_pass(P, t->W, &P2, &W2);
+            pt::AdamParams A2 = A;
+            A2.m[0] = A.m[3]; A2.m[1] = A.m[4];
+            A2.v[0] = A.v[3]; A2.v[1] = A.v[4];
+            PT_HIP(pt::launch_apply_adam(P2, W2, A2, bs, 0.f, 0.f, nullptr, st));
+        }
         ++t->adam_step;
     } else {
         P.inv_count = scale;   // (the apply pass reads these two for the loss only)
         P.margin = cst;
         PT_HIP(pt::launch_apply(P, t->W, nullptr, 0, bs, 1 + 2 * neg, d_loss, st));
+        if (transd) {
+            pt::StepParams P2;
+            pt::StepWorkspace W2;
+            pt::transd_transfer_pass(P, t->W, &P2, &W2);
+            PT_HIP(pt::launch_apply(P2, W2, nullptr, 0, bs, 1 + 2 * neg, nullptr, st));
+        }
     }
     if (ev) PT_HIP(hipEventRecord(ev[2], st));
     return PT_OK;
 }
 
 static const char *kExtendedMsg =
-    "a non-default loss (pt_trainer_set_loss) and PT_ADAM train external batches only: in-kernel sampling, captured "
-    "runs and the reference-order mode are not implemented for them";
+    "a non-default loss (pt_trainer_set_loss), PT_ADAM and PT_TRANSD train external batches only: in-kernel sampling, "
+    "captured runs and the reference-order mode are not implemented for them";
 
 // per-positive loss partials for batches of up to `bs` positives (grown on demand, never during a
 // capture: callers prepare before enqueueing)
@@ -545,6 +573,7 @@ extern "C" int pt_trainer_set_sample_split(pt_trainer *t, int64_t head) {
 extern "C" int pt_trainer_set_deterministic(pt_trainer *t, int32_t on) {
     PT_CHECK(t, PT_EINVAL, "null trainer");
     PT_CHECK(!on || pt::ordered_dim_supported(t->P.dim), PT_ENOTSUP, "reference-order mode: dim too large");
+    PT_CHECK(!on || t->P.model != PT_TRANSD, PT_ENOTSUP, "reference-order mode is not implemented for TransD");
     t->ordered = on != 0;
     return PT_OK;
 }
@@ -568,12 +597,17 @@ extern "C" int pt_trainer_set_loss(pt_trainer *t, const pt_loss_desc *l) {
 
 extern "C" int pt_trainer_set_adam(pt_trainer *t, const pt_adam_state *a) {
     PT_CHECK(t && a, PT_EINVAL, "pt_trainer_set_adam: null argument");
-    PT_CHECK(a->ent_m && a->ent_v && a->rel_m && a->rel_v && (t->P.model == PT_TRANSE || (a->norm_m && a->norm_v)),
+    PT_CHECK(a->ent_m && a->ent_v && a->rel_m && a->rel_v && (t->P.model != PT_TRANSH || (a->norm_m && a->norm_v)) &&
+                 (t->P.model != PT_TRANSD ||
+                  (a->ent_transfer_m && a->ent_transfer_v && a->rel_transfer_m && a->rel_transfer_v)),
              PT_EINVAL, "Adam needs exp_avg and exp_avg_sq buffers for every table");
     PT_CHECK(a->beta1 >= 0. && a->beta1 < 1. && a->beta2 >= 0. && a->beta2 < 1. && a->eps >= 0. && a->step >= 0,
              PT_EINVAL, "Adam: betas must be in [0, 1), eps and step non-negative");
     t->adam.m[0] = a->ent_m; t->adam.m[1] = a->rel_m; t->adam.m[2] = a->norm_m;
     t->adam.v[0] = a->ent_v; t->adam.v[1] = a->rel_v; t->adam.v[2] = a->norm_v;
+    const bool td = t->P.model == PT_TRANSD;   // (the appended fields are read for TransD only)
+    t->adam.m[3] = td ? a->ent_transfer_m : nullptr; t->adam.m[4] = td ? a->rel_transfer_m : nullptr;
+    t->adam.v[3] = td ? a->ent_transfer_v : nullptr; t->adam.v[4] = td ? a->rel_transfer_v : nullptr;
     t->adam.beta1 = a->beta1; t->adam.beta2 = a->beta2; t->adam.eps = a->eps;
     t->adam_step = a->step;
     t->adam_set = true;

@@ -466,6 +466,9 @@ class Parallel_Universe_Config(Tester):
     def _check_setup(self):
         if self.embedding_model is None or getattr(self.embedding_model, "native_model", None) is None:
             raise NotImplementedError("embedding_model must be openke.module.model.TransE or TransH")
+        if self.embedding_model.native_model == _native.PT_TRANSD:
+            raise NotImplementedError("PuTransD is not built yet: TransD trains and ranks one model (Trainer, Tester), "
+                                      "its universes are not implemented")
         _native.require_gpu()
 
     def _universe_draws(self, uid):

@@ -9,7 +9,8 @@ touched rows only (identical to the reference's dense update). Losses stay on th
 end of the epoch (one host sync per epoch instead of one per step). Cross sampling and relation
 corruption (neg_rel > 0) train batch by batch: GPU-sampled batch, then the external-batch step. So do
 TransE under SigmoidLoss, the self-adversarial weights (adv_temperature) or a model margin (k_step_adv),
-and Adam (k_apply_adam, dense) for either model."""
+and Adam (k_apply_adam, dense) for either model, and every TransD step (k_step_transd: plain MarginLoss with SGD,
+Adagrad or Adam)."""
 import ctypes
 import os
 
@@ -111,6 +112,8 @@ class Trainer(object):
         if self.deterministic and (weighted or opt.method == _native.PT_ADAM):
             raise NotImplementedError("deterministic=True (reference-order mode) covers plain MarginLoss with SGD or "
                                       "Adagrad only")
+        if self.deterministic and kge.native_model == _native.PT_TRANSD:
+            raise NotImplementedError("deterministic=True (reference-order mode) is not implemented for TransD")
         margin = float(loss.margin.item()) if isinstance(loss, MarginLoss) else 0.0
         desc = kge.native_desc(opt.method, opt.lr, margin, opt.state_sum)
         key = (id(kge), kge.tables()[0].data_ptr(), opt.method, opt.lr, margin)
@@ -132,8 +135,11 @@ class Trainer(object):
         _native.check(L.pt_trainer_set_loss(self._native, ctypes.byref(ld)))
         if opt.method == _native.PT_ADAM:
             a = _native.AdamState()
-            a.ent_m, a.rel_m, a.norm_m = (_native.ptr(x) for x in opt.exp_avg)
-            a.ent_v, a.rel_v, a.norm_v = (_native.ptr(x) for x in opt.exp_avg_sq)
+            a.ent_m, a.rel_m, a.norm_m = (_native.ptr(x) for x in opt.exp_avg[:3])
+            a.ent_v, a.rel_v, a.norm_v = (_native.ptr(x) for x in opt.exp_avg_sq[:3])
+            if len(opt.exp_avg) == 5:   # TransD: the two transfer tables' moments
+                a.ent_transfer_m, a.rel_transfer_m = (_native.ptr(x) for x in opt.exp_avg[3:])
+                a.ent_transfer_v, a.rel_transfer_v = (_native.ptr(x) for x in opt.exp_avg_sq[3:])
             a.beta1, a.beta2 = opt.betas
             a.eps = opt.eps
             a.step = int(opt.step)
@@ -142,7 +148,8 @@ class Trainer(object):
 
     def _external_only(self, kge, loss):
         """Whether every step goes through the external-batch step (k_step / k_step_adv + k_apply / k_apply_adam)."""
-        return self._weighted(kge, loss) or self.optimizer.method == _native.PT_ADAM
+        return (self._weighted(kge, loss) or self.optimizer.method == _native.PT_ADAM
+                or kge.native_model == _native.PT_TRANSD)
 
     def _sync_step(self):
         if self.optimizer.method == _native.PT_ADAM:

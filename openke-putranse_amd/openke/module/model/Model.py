@@ -237,13 +237,14 @@ class Model(BaseModule):
 
     # -- native plumbing --------------------------------------------------------------------------
     def tables(self):
-        """(ent, rel, norm_vector or None) weight tensors."""
+        """(ent, rel, norm_vector or None) weight tensors; TransD appends (ent_transfer, rel_transfer)."""
         nv = getattr(self, "norm_vector", None)
         return (self.ent_embeddings.weight, self.rel_embeddings.weight, nv.weight if nv is not None else None)
 
     def native_desc(self, opt=_native.PT_SGD, lr=0.0, margin=0.0, accs=(None, None, None)):
-        ent, rel, nv = self.tables()
-        for t in (ent, rel, nv):
+        tabs = self.tables()
+        ent, rel, nv = tabs[:3]
+        for t in tabs:
             if t is None:
                 continue
             if not t.is_cuda:
@@ -264,10 +265,15 @@ class Model(BaseModule):
         d.ent = ent.data_ptr()
         d.rel = rel.data_ptr()
         d.normv = nv.data_ptr() if nv is not None else None
-        ea, ra, na = accs
+        ea, ra, na = accs[:3]
         d.ent_acc = ea.data_ptr() if ea is not None else None
         d.rel_acc = ra.data_ptr() if ra is not None else None
         d.norm_acc = na.data_ptr() if na is not None else None
+        if len(tabs) == 5:   # TransD: the two transfer tables and their Adagrad state
+            d.ent_transfer, d.rel_transfer = tabs[3].data_ptr(), tabs[4].data_ptr()
+            eta, rta = accs[3:5] if len(accs) == 5 else (None, None)
+            d.ent_transfer_acc = eta.data_ptr() if eta is not None else None
+            d.rel_transfer_acc = rta.data_ptr() if rta is not None else None
         return d
 
     def _ids(self, x, dev):

@@ -3,5 +3,6 @@ from __future__ import absolute_import, division, print_function
 from .Model import Model
 from .TransE import TransE
 from .TransH import TransH
+from .TransD import TransD
 
-__all__ = ['Model', 'TransE', 'TransH']
+__all__ = ['Model', 'TransE', 'TransH', 'TransD']
