@@ -116,6 +116,11 @@ int pt_trainer_step(pt_trainer *t, pt_sampler *sampler, int64_t bs, int64_t neg,
  * (captured once into a hipGraph per shape and replayed). d_losses[s] receives step s's loss. */
 int pt_trainer_run(pt_trainer *t, pt_sampler *sampler, int64_t bs, int64_t neg, int64_t bern, int64_t filter,
                    int64_t steps, float *d_losses, void *stream);
+/* 1 when pt_trainer_run takes batches of bs x neg on this trainer (its model, dim, loss, optimizer and mode), else 0:
+ * the caller then trains the same batches one by one (pt_sampler_sample_ex + pt_trainer_step on external batches).
+ * At dims above 512 the fused run exists for TransE with neg >= 4 while the entity, relation and bs * neg
+ * contribution rows stay under 2^31 bytes, and for the reference-order mode. No device call. */
+int pt_trainer_fused_supported(const pt_trainer *t, int64_t bs, int64_t neg);
 
 /* Sampling path of the trainer's in-kernel-sampled chunks (neg >= 4): path = PT_PATH_FUSED / PT_PATH_PART /
  * PT_PATH_TWO_PASS (where its LDS plan fits) or -1 (automatic: fused for chunks of >= 96 steps, else the split
@@ -302,6 +307,10 @@ int pt_universe_set_launch_times(pt_universe_set *s, int64_t cap, float *out, in
 /* 1 when universes of embedding dim `dim` train on the fast universe kernels (model PT_TRANSE / PT_TRANSH),
  * else 0 (pt_universe_set_create then fails with PT_EINVAL). No device call. */
 int pt_universe_dim_supported(int64_t dim, int32_t model);
+/* 1 when a single model of embedding dim `dim` is accepted by pt_trainer_create / pt_score* (pt_model_desc.dim):
+ * PT_TRANSE / PT_TRANSH at dims 1..512 and at multiples of 4 from 516 to 1024 (float4 rows), PT_TRANSD at dims
+ * 1..512; else 0 (those calls then fail with PT_ENOTSUP). No device call. */
+int pt_model_dim_supported(int64_t dim, int32_t model);
 /* reference-order (deterministic) mode of a set (see pt_trainer_set_deterministic): one workgroup per
  * universe runs its steps with the ordered per-row sums; its workspace is allocated on first use */
 int pt_universe_set_deterministic(pt_universe_set *s, int32_t on);

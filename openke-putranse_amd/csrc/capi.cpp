@@ -46,7 +46,11 @@ int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
     PT_CHECK(m->p_norm == 1 || m->p_norm == 2, PT_ENOTSUP, "p_norm must be 1 or 2");
     PT_CHECK(m->opt == PT_SGD || m->opt == PT_ADAGRAD || m->opt == PT_ADAM, PT_EINVAL,
              "opt must be PT_SGD, PT_ADAGRAD or PT_ADAM");
-    PT_CHECK(pt::shape_supported(m->dim), PT_ENOTSUP, "embedding dim " + std::to_string(m->dim) + " not supported");
+    PT_CHECK(m->model != PT_TRANSD || pt::model_dim_supported(m->dim, m->model), PT_ENOTSUP,
+             "embedding dim " + std::to_string(m->dim) + " not supported: TransD takes dims 1..512");
+    PT_CHECK(pt::model_dim_supported(m->dim, m->model), PT_ENOTSUP,
+             "embedding dim " + std::to_string(m->dim) +
+                 " not supported: TransE and TransH take dims 1..512 and multiples of 4 from 516 to 1024");
     PT_CHECK(m->ent && m->rel && m->ent_total > 0 && m->rel_total > 0, PT_EINVAL, "missing tables");
     PT_CHECK(m->model != PT_TRANSH || m->normv, PT_EINVAL, "TransH needs norm_vector");
     PT_CHECK(m->model != PT_TRANSD || (m->ent_transfer && m->rel_transfer), PT_EINVAL,
@@ -71,6 +75,10 @@ int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
     }
     if (const char *v = pt_tuning_env("PT_STEP_DBG")) P.dbg = atoi(v);
     return PT_OK;
+}
+
+extern "C" int pt_model_dim_supported(int64_t dim, int32_t model) {
+    return pt::model_dim_supported(dim, model) ? 1 : 0;
 }
 
 // ======================================================================== graphs =================
@@ -341,14 +349,15 @@ extern "C" int pt_lp_min_scores(const pt_lp_universe *us, int64_t n_universes, i
     PT_CHECK((us && pairs && d_key_rows) || n_pairs == 0, PT_EINVAL, "pt_lp_min_scores: null argument");
     if (n_pairs == 0) return PT_OK;
     hipStream_t st = (hipStream_t)stream;
-    // per universe once: its dim's row shape is instantiated, and the job key of that shape (below)
+    // per universe once: its dim is at most 512 (the scan's LDS tile of 64 x (dim + 1) floats, and its one-float
+    // rows), and the job key of its row shape (below)
     auto shape_key = [](int64_t dim) {
         const pt::Shape s = pt::pick_shape(dim);
         return (int64_t)s.G * 10000 + (int64_t)s.VEC * 100 + s.KCH;
     };
     std::vector<int64_t> u_shape((size_t)n_universes, -1);
     for (int64_t u = 0; u < n_universes; ++u)
-        if (pt::shape_supported(us[u].dim)) u_shape[(size_t)u] = shape_key(us[u].dim);
+        if (pt::narrow_dim_supported(us[u].dim)) u_shape[(size_t)u] = shape_key(us[u].dim);
     for (int64_t i = 0; i < n_pairs; ++i) {
         const pt_lp_pair &p = pairs[i];
         PT_CHECK(p.universe >= 0 && p.universe < n_universes, PT_EINVAL, "pair universe out of range");

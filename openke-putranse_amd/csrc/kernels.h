@@ -104,9 +104,11 @@ constexpr Shape pick_shape(int64_t D, bool vec4 = true) {
     return Shape{G, VEC, KCH};
 }
 
-// instantiated (G, VEC, KCH) row shapes
+// instantiated (G, VEC, KCH) row shapes: float4 rows up to dim 1,024 (KCH 3 and 4: dims 516..1,024, TransE and TransH
+// single models only; model_dim_supported is the rule), one-float rows up to dim 512
 #define PT_SHAPES(X)                                                                                  \
-    X(2, 4, 1) X(4, 4, 1) X(8, 4, 1) X(16, 4, 1) X(32, 4, 1) X(64, 4, 1) X(64, 4, 2)                 \
+    X(2, 4, 1) X(4, 4, 1) X(8, 4, 1) X(16, 4, 1) X(32, 4, 1) X(64, 4, 1) X(64, 4, 2) X(64, 4, 3)     \
+    X(64, 4, 4)                                                                                       \
     X(2, 1, 1) X(4, 1, 1) X(8, 1, 1) X(16, 1, 1) X(32, 1, 1) X(64, 1, 1) X(64, 1, 2) X(64, 1, 4)    \
     X(64, 1, 8)
 
@@ -134,7 +136,11 @@ constexpr bool for_value(int v, F &&f) {
     return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
 }
 
-bool shape_supported(int64_t dim);
+// The one dim rule of the single-model path (pt_model_dim_supported): dims 1..512 for every model (both row layouts
+// exist), dims 516..1,024 in multiples of 4 (float4 rows only) for TransE (0) and TransH (1); nothing else
+bool model_dim_supported(int64_t dim, int model);
+// dims at which both row layouts exist (1..512): what the one-float kernels (k_step_sampled, k_lp_scan_t's tile) take
+bool narrow_dim_supported(int64_t dim);
 hipError_t launch_sample(const DeviceGraph &g, const uint64_t *states, int64_t threads, int64_t bs, int64_t neg,
                          int64_t neg_rel, int mode, int bern, int filter, int64_t *h, int64_t *t, int64_t *r, float *y,
                          hipStream_t st);

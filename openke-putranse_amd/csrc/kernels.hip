@@ -946,18 +946,32 @@ __global__ __launch_bounds__(64 * NW) void k_lp_scan_t(const LpUniverseDev *__re
 
 // ==================================================================== host launchers ===========
 constexpr bool shape_listed(const Shape &s) { return for_shape(s, [](auto) {}); }
-constexpr bool dim_dispatches(int64_t dim) {
-    return shape_listed(pick_shape(dim)) && shape_listed(pick_shape(dim, false));
+// dims 1..512 have their instances under both layouts; dims 516..1,024 in multiples of 4 under the float4 layout only
+constexpr bool narrow_dispatches(int64_t dim) {
+    return dim >= 1 && dim <= 512 && shape_listed(pick_shape(dim)) && shape_listed(pick_shape(dim, false));
 }
-// every dim up to 512 has its instances under both layouts; the first dims past it (VEC = 1, VEC = 4) do not
-constexpr bool dims_1_to_512_dispatch() {
+constexpr bool wide_dispatches(int64_t dim) {
+    return dim > 512 && dim <= 1024 && dim % 4 == 0 && shape_listed(pick_shape(dim));
+}
+constexpr bool dim_dispatches(int64_t dim, int model) {
+    return narrow_dispatches(dim) || ((model == 0 || model == 1) && wide_dispatches(dim));
+}
+constexpr bool dim_rule_holds() {
     for (int64_t dim = 1; dim <= 512; ++dim)
-        if (!dim_dispatches(dim)) return false;
-    return !dim_dispatches(513) && !dim_dispatches(516);
+        for (int model = 0; model < 3; ++model)
+            if (!dim_dispatches(dim, model)) return false;
+    for (int64_t dim = 513; dim <= 1100; ++dim)
+        for (int model = 0; model < 3; ++model)
+            if (dim_dispatches(dim, model) != (model < 2 && dim <= 1024 && dim % 4 == 0)) return false;
+    return !dim_dispatches(0, 0) && !dim_dispatches(513, 0) && !dim_dispatches(514, 0) && !dim_dispatches(1028, 0) &&
+           !dim_dispatches(516, 2);
 }
-static_assert(dims_1_to_512_dispatch(), "PT_SHAPES does not cover pick_shape over dims 1..512");
+static_assert(dim_rule_holds(),
+              "PT_SHAPES must cover dims 1..512 under both layouts and dims 516..1024 (multiples of 4) as float4 rows "
+              "for TransE / TransH; 513, 514, 1028 and TransD above 512 must not dispatch");
 
-bool shape_supported(int64_t dim) { return dim > 0 && dim_dispatches(dim); }
+bool model_dim_supported(int64_t dim, int model) { return model >= 0 && model <= 2 && dim_dispatches(dim, model); }
+bool narrow_dim_supported(int64_t dim) { return narrow_dispatches(dim); }
 
 hipError_t launch_sample(const DeviceGraph &g, const uint64_t *states, int64_t threads, int64_t bs, int64_t neg,
                          int64_t neg_rel, int mode, int bern, int filter, int64_t *h, int64_t *t, int64_t *r, float *y,
@@ -1128,21 +1142,25 @@ hipError_t launch_lp_min(const LpUniverseDev *us, const LpPair *pairs, int64_t n
     for_shape(s, [&](auto sh) {
         for_value<0, 1>(model != 0, [&](auto m) {
             using T = decltype(sh);
-            const auto scan = dev::k_lp_scan_t<m.value, kLpWaves>;
-            if (lds_t > (64 << 10)) {
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(scan),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
-                if (e != hipSuccess) return;
+            // (the shapes of dims above 512, which pt_lp_min_scores refuses, have no instance here)
+            if constexpr (T::VEC * T::KCH <= 8) {
+                const auto scan = dev::k_lp_scan_t<m.value, kLpWaves>;
+                if (lds_t > (64 << 10)) {
+                    e = hipFuncSetAttribute(reinterpret_cast<const void *>(scan),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
+                    if (e != hipSuccess) return;
+                }
+                for (int64_t y0 = 0; y0 < n_active; y0 += 65535) {   // (grid.y holds 65,535 universes)
+                    if (y0 == 0)
+                        hipLaunchKernelGGL((dev::k_lp_bases<m.value, T::G, T::VEC, T::KCH>), gb, block, 0, st, us,
+                                           pairs, n_pairs, p_norm, norm_flag, ds, base, normal, tuple_min);
+                    const dim3 gt((unsigned)((max_ent + 63) / 64),
+                                  (unsigned)(n_active - y0 < 65535 ? n_active - y0 : 65535));
+                    hipLaunchKernelGGL(scan, gt, bt, lds_t, st, us, pairs, uoff, uids + y0, p_norm, norm_flag, global_E,
+                                       ds, base, normal, rows);
+                }
+                e = hipGetLastError();
             }
-            for (int64_t y0 = 0; y0 < n_active; y0 += 65535) {   // (grid.y holds 65,535 universes)
-                if (y0 == 0)
-                    hipLaunchKernelGGL((dev::k_lp_bases<m.value, T::G, T::VEC, T::KCH>), gb, block, 0, st, us, pairs,
-                                       n_pairs, p_norm, norm_flag, ds, base, normal, tuple_min);
-                const dim3 gt((unsigned)((max_ent + 63) / 64), (unsigned)(n_active - y0 < 65535 ? n_active - y0 : 65535));
-                hipLaunchKernelGGL(scan, gt, bt, lds_t, st, us, pairs, uoff, uids + y0, p_norm, norm_flag, global_E, ds,
-                                   base, normal, rows);
-            }
-            e = hipGetLastError();
         });
     });
     return e;

@@ -572,6 +572,11 @@ int pick_nch(int64_t neg, int kch) {
 // k_step_csr's instances are the VEC = 4 rows of PT_SHAPES x S in {1, 2, 4} x p_norm, with chunks of kCsrNch rows.
 // C2 (S = 4, 7 negatives per group): chunks of 2 rows, double-buffered, measured fastest
 static constexpr int kCsrNch = 2;
+// the chunk depth by shape: single rows where one lane group walks all of a positive's negatives (S = 1) with 16
+// floats per lane (KCH 4, dims 772..1,024): two double-buffered rows of that width leave one wave per SIMD with
+// values parked in AGPRs, and single rows measured 7 % faster at steady state (69.3 against 74.5 us per step at dim
+// 1,024, 8 negatives); kCsrNch everywhere else, where the two depths measured level or two ahead
+constexpr int csr_nch(int kch, int s) { return kch >= 4 && s == 1 ? 1 : kCsrNch; }
 
 // TransE on the counting-sort path with float4 rows takes k_step_csr (the contribution rows always count
 // towards the offsets' 31 bits)
@@ -585,6 +590,7 @@ bool step_fits(const StepParams &P0, int64_t neg, bool csr) {
     StepParams P = P0;
     P.neg = neg;
     if (csr && csr_fast_path(P)) return true;
+    if (!narrow_dim_supported(P.dim)) return false;   // k_step_sampled has one-float rows only (dims to 512)
     const Shape s = pick_shape(P.dim, false);
     const int S = (neg >= 8 && 256 / s.G >= 4) ? 4 : 1;
     const int64_t gpb = 256 / s.G, ppb = gpb / S;
@@ -627,8 +633,21 @@ hipError_t launch_step(const StepParams &P, const DeviceGraph &g, const uint64_t
                     for_value<1, 2>(P.p_norm == 1 ? 1 : 2, [&](auto pn) {
                         constexpr int SG = sv.value * T::G, NT = SG >= 256 || 256 % SG != 0 ? SG : 256;
                         const dim3 grid((unsigned)((P.batch_size * SG + NT - 1) / NT)), block(NT);
-                        hipLaunchKernelGGL((dev::k_step_csr<T::G, 4, T::KCH, kCsrNch, sv.value, pn.value, NT>), grid,
-                                           block, 0, st, P, sink, *csr);
+#ifdef PT_TUNING
+                        // PT_CSR_NCH=1|2: the chunk depth of the wide shapes, for the A/B timing behind csr_nch
+                        if constexpr (T::KCH > 2) {
+                            const char *v = pt_tuning_env("PT_CSR_NCH");
+                            const bool forced = v && for_value<1, 2>(atoi(v), [&](auto n) {
+                                hipLaunchKernelGGL((dev::k_step_csr<T::G, 4, T::KCH, n.value, sv.value, pn.value, NT>),
+                                                   grid, block, 0, st, P, sink, *csr);
+                                e = hipGetLastError();
+                            });
+                            if (forced) return;
+                        }
+#endif
+                        constexpr int NCH = csr_nch(T::KCH, sv.value);
+                        hipLaunchKernelGGL((dev::k_step_csr<T::G, 4, T::KCH, NCH, sv.value, pn.value, NT>), grid, block,
+                                           0, st, P, sink, *csr);
                         e = hipGetLastError();
                     });
                 });

@@ -284,6 +284,11 @@ __global__ __launch_bounds__(256) void k_step_adv(StepParams P, LossParams L, co
 static constexpr int64_t kAdvLdsFloats = 64 * 1024 / 4;
 static int64_t adv_row_floats(const Shape &s) { return s.VEC == 4 ? (int64_t)s.KCH * s.G * s.VEC : 0; }
 int64_t step_adv_max_neg(int64_t dim) { return kAdvLdsFloats - adv_row_floats(pick_shape(dim)); }
+// rows of negatives in flight per chunk (NCH): 4 where a lane holds up to 8 floats of a row; 2 at 12 and 16 floats
+// (KCH 3 and 4, dims 516..1,024), where 4 rows in flight leave one wave per SIMD (256 VGPRs) - as k_step_transd
+// drops to 2 at 8 floats per lane. The rule rests on dim 768 (KCH 3), where 4 rows measured 17 % slower than 2
+// (487.8 against 415.1 us); at dim 1,024 the depths 1, 2 and 4 tie within 1 %
+constexpr int adv_nch(int vec, int kch) { return vec * kch > 8 ? 2 : 4; }
 
 hipError_t launch_step_adv(const StepParams &P, const LossParams &L, const int64_t *bh, const int64_t *bt,
                            const int64_t *br, const StepWorkspace &W, hipStream_t st) {
@@ -326,8 +331,21 @@ hipError_t launch_step_adv(const StepParams &P, const LossParams &L, const int64
     hipError_t e = hipErrorInvalidValue;
     for_shape(s, [&](auto sh) {
         using T = decltype(sh);
-        hipLaunchKernelGGL((dev::k_step_adv<T::G, T::VEC, T::KCH, 4>), grid, block, lds, st, P, L, bh, bt, br, sink,
-                           W.lpart);
+#ifdef PT_TUNING
+        // PT_ADV_NCH=1|2|4: the chunk depth of the wide shapes, for the A/B timing behind adv_nch
+        if (const char *v = pt_tuning_env("PT_ADV_NCH")) {
+            if constexpr (T::VEC * T::KCH > 8) {
+                const bool forced = for_value<1, 2, 4>(atoi(v), [&](auto n) {
+                    hipLaunchKernelGGL((dev::k_step_adv<T::G, T::VEC, T::KCH, n.value>), grid, block, lds, st, P, L, bh,
+                                       bt, br, sink, W.lpart);
+                    e = hipGetLastError();
+                });
+                if (forced) return;
+            }
+        }
+#endif
+        hipLaunchKernelGGL((dev::k_step_adv<T::G, T::VEC, T::KCH, adv_nch(T::VEC, T::KCH)>), grid, block, lds, st, P, L,
+                           bh, bt, br, sink, W.lpart);
         e = hipGetLastError();
     });
     return e;

@@ -104,8 +104,20 @@ int check_step_args(const pt::StepParams &P, pt_sampler *s, int64_t bs, int64_t 
     PT_CHECK(s->g->ent_total > 1, PT_EINVAL, "graph needs at least two entities");
     pt::StepParams Q = P;
     Q.batch_size = bs;
+    PT_CHECK(pt::narrow_dim_supported(P.dim) || pt::step_fits(Q, neg, use_csr(neg)), PT_ENOTSUP,
+             "in-kernel sampling at dims above 512 trains TransE with neg_ent >= 4 and tables plus contribution rows "
+             "under 2^31 bytes (pt_trainer_fused_supported): train external batches instead");
     PT_CHECK(pt::step_fits(Q, neg, use_csr(neg)), PT_ENOTSUP, "neg_ent too large for the LDS draw buffer");
     return PT_OK;
+}
+
+// whether pt_trainer_run takes (bs, neg): the checks it makes on the trainer itself, in its order
+bool fused_supported(const pt_trainer *t, int64_t bs, int64_t neg) {
+    if (t->extended() || bs <= 0 || neg <= 0) return false;
+    if (t->ordered) return true;
+    pt::StepParams Q = t->P;
+    Q.batch_size = bs;
+    return pt::step_fits(Q, neg, use_csr(neg));
 }
 
 }  // namespace
@@ -863,6 +875,10 @@ extern "C" int pt_trainer_sample_csr(pt_trainer *t, pt_sampler *s, int64_t bs, i
         h_pos[3 * i + 2] = pos[i].z;
     }
     return PT_OK;
+}
+
+extern "C" int pt_trainer_fused_supported(const pt_trainer *t, int64_t bs, int64_t neg) {
+    return t && fused_supported(t, bs, neg) ? 1 : 0;
 }
 
 extern "C" int pt_trainer_run(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, int64_t bern, int64_t filter,

@@ -238,6 +238,12 @@ class Trainer(object):
         dev = kge.ent_embeddings.weight.device
         losses = torch.zeros(max(nb, 1), dtype=torch.float32, device=dev)
         fused = dl.sampling_mode == "normal" and dl.negative_rel == 0 and not self._external_only(kge, loss)
+        # at dims above 512 the library says whether its fused run takes this model at (bs, neg): TransH, neg < 4 and
+        # TransE past the 31-bit row offsets train the same batches through the external-batch loop. (At dims up to
+        # 512 pt_trainer_run answers for itself, as before.)
+        if fused and kge.ent_embeddings.weight.shape[1] > 512:
+            fused = nb > 0 and bool(L.pt_trainer_fused_supported(self._native, bs, neg))
+        self.last_run_fused = fused
         buf = None
         if not fused:
             seq = bs * (1 + neg + dl.negative_rel)

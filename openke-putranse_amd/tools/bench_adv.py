@@ -1,8 +1,8 @@
 """Measure the self-adversarial TransE step (k_step_adv + k_apply_adam) against the same step in torch ops.
 
 Shape: a WN18RR-shaped synthetic graph (tools/synth_kg.py: 40,943 entities, 11 relations), batch 2000, 64 negatives,
-cross sampling, dim 512, p 1, norm_flag off, model margin 6, SigmoidLoss(adv_temperature=1), Adam at lr 2e-5 - the
-recipe of examples/train_transe_WN18_adv_sigmoidloss.py at the largest dim the row shapes hold.
+cross sampling, dim 512 (--dim 1024 is the example's own), p 1, norm_flag off, model margin 6,
+SigmoidLoss(adv_temperature=1), Adam at lr 2e-5 - the recipe of examples/train_transe_WN18_adv_sigmoidloss.py.
 
 One process, device events, 20 warm-up steps, then the median of 5 runs of 100 steps of
   * k_step_adv and k_apply_adam each on its own (pt_trainer_steps_timed: events around both launches of a step),
@@ -13,7 +13,9 @@ One process, device events, 20 warm-up steps, then the median of 5 runs of 100 s
 The per-kernel figures repeat ONE device batch, so every step touches the same 128,000 corrupted rows and the same
 flagged rows: a friendlier cache state than training's fresh batches. The whole-step figures use fresh batches.
 --lib PATH loads another build of the library (the measurement build, `make TUNING=1`, whose PT_ADV_STAGE=1 selects
-the LDS-staged pass 2 of k_step_adv) and records the variant under "pass2".
+the LDS-staged pass 2 of k_step_adv and whose PT_ADV_NCH=1|2|4 sets the chunk depth of the shapes above dim 512) and
+records the variant under "pass2" / "k_step_adv_chunk_depth". k_step_adv is also reported against its float-atomic
+floor (the batch's corrupted rows at 1.3 TB/s), k_apply_adam against its six-pass HBM floor at 6.29 TB/s.
 Prints one JSON line; --out also writes it to a file. Needs a GPU: there is no CPU path.
 """
 import argparse
@@ -42,6 +44,7 @@ def main():
     ap.add_argument("--data-dir", default=os.path.join(tempfile.gettempdir(), "putranse_bench_adv_%d" % os.getuid()))
     ap.add_argument("--out", default=None)
     ap.add_argument("--lib", default=None, help="another build of libputranse_hip.so (measurement build)")
+    ap.add_argument("--skip-torch", action="store_true", help="leave out the torch-op step (A/B runs of the kernels)")
     args = ap.parse_args()
 
     import numpy as np
@@ -146,13 +149,17 @@ def main():
         for _ in range(n):
             torch_step()
 
-    torch_run(args.warmup)
-    torch_us = [timed(lambda: torch_run(steps)) for _ in range(args.runs)]
+    torch_us = None   # (--skip-torch: the three torch figures are written as null)
+    if not args.skip_torch:
+        torch_run(args.warmup)
+        torch_us = [timed(lambda: torch_run(steps)) for _ in range(args.runs)]
 
     med = statistics.median
     rows = E + R
     floor_bytes = 6 * rows * D * 4   # w, m, v read and written
     hbm = 6.29e12                    # measured float4-copy bandwidth of the MI355X (bytes / s)
+    atomic_bytes = bs * neg * D * 4  # the corrupted rows, added atomically
+    atomic_rate = 1.3e12             # the chip's float-atomic rate
     res = {
         "tool": "bench_adv", "device": torch.cuda.get_device_name(0),
         "shape": {"entities": E, "relations": R, "batch": bs, "neg": neg, "dim": D, "p_norm": 1, "norm_flag": False,
@@ -160,16 +167,20 @@ def main():
                   "sampling": "cross"},
         "steps": steps, "warmup": args.warmup, "runs": args.runs,
         "k_step_adv_us": med(k_step), "k_step_adv_us_runs": k_step,
+        "k_step_adv_atomic_floor_bytes": atomic_bytes,
+        "k_step_adv_atomic_floor_us_at_1.3TBps": atomic_bytes / atomic_rate * 1e6,
+        "k_step_adv_fraction_of_atomic_floor": (atomic_bytes / atomic_rate * 1e6) / med(k_step),
+        "k_step_adv_chunk_depth": (os.environ.get("PT_ADV_NCH") if args.lib else None) or "default",
         "k_apply_adam_us": med(k_adam), "k_apply_adam_us_runs": k_adam,
         "k_apply_adam_floor_bytes": floor_bytes,
         "k_apply_adam_floor_us_at_6.29TBps": floor_bytes / hbm * 1e6,
         "k_apply_adam_fraction_of_floor": (floor_bytes / hbm * 1e6) / med(k_adam),
         "native_step_us": med(whole), "native_step_us_runs": whole,
-        "torch_step_us": med(torch_us), "torch_step_us_runs": torch_us,
-        "native_over_torch_speedup": med(torch_us) / med(whole),
+        "torch_step_us": med(torch_us) if torch_us else None, "torch_step_us_runs": torch_us,
+        "native_over_torch_speedup": med(torch_us) / med(whole) if torch_us else None,
         "pass2": "pass-1 rows staged in LDS" if staged else "re-reads rows (L2 / Infinity Cache)",
         "kernel_figures_note": "one repeated device batch (same rows every step); whole-step figures use fresh batches",
-        "last_loss_native": native_loss, "last_loss_torch": float(last[0]),
+        "last_loss_native": native_loss, "last_loss_torch": float(last[0]) if torch_us else None,
     }
     line = json.dumps(res)
     print(line)
