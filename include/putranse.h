@@ -127,11 +127,9 @@ int pt_trainer_fused_supported(const pt_trainer *t, int64_t bs, int64_t neg);
  * sampler); parts = workgroups per call of the split sampler (0 = automatic, ceil(512 / calls)). Every path
  * draws the same batches (bit-exact); this selects only how. */
 int pt_trainer_set_sampling(pt_trainer *t, int32_t path, int64_t parts);
-/* Two-launch split sampling. Training (pt_trainer_run) no longer uses it: sampling a chunk's first `head` steps
- * ahead and the rest on a side stream beside the first steps' training was measured slower,
- * and every chunk of a run is sampled by one launch. The setter still selects how pt_trainer_sample_csr samples a
- * PT_PATH_PART chunk (same batches, bit-exact): `head` calls by one launch, the rest by a second on the trainer's
- * side stream. head = 0 or -1 (the default): one launch; a chunk of <= head calls is sampled in one launch. */
+/* Compatibility shim of the removed two-launch split sampling (a chunk's first `head` steps sampled ahead, the rest
+ * on a side stream; measured slower and removed: DESIGN.md section 4). The setter accepts head = 0 or -1 (PT_OK) and
+ * answers PT_ENOTSUP to head > 0 (PT_EINVAL for a null trainer or head < -1). */
 int pt_trainer_set_sample_split(pt_trainer *t, int64_t head);
 /* Reference-order (deterministic) mode of a trainer: every later pt_trainer_step / pt_trainer_run sums each
  * table row's gradient in slot order, lookup by lookup (batch_h, batch_t, batch_r; norm_vector(batch_r)),

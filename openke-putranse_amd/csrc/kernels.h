@@ -1,4 +1,4 @@
-// Host-side launch interface of the HIP kernels (kernels.hip).
+// Host-side launch interface of the HIP kernels (kernels.hip and the other .hip files).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -49,8 +49,7 @@ struct CsrWork {
     int32_t *cnt = nullptr;     // [calls][cnt_stride] bucket sizes (zero between uses)
     int32_t *start = nullptr;   // [calls][start_stride] exclusive prefix of cnt (E+1 used)
     float *contrib = nullptr;   // [bs*neg][dim] gradient rows of the corrupted entities (one step)
-    int32_t *tick = nullptr;    // [calls + 1] parts of a call done, then calls done (k_sample_part; zero
-                                // between uses)
+    int32_t *tick = nullptr;    // [calls + 1] parts of a call done, then calls done (k_sample_part; zero between uses)
     int rank_only = 0;          // off[] holds bucket ranks (k_sample_part) instead of destinations
     uint64_t *prof = nullptr;   // PT_PART_PROF=1 only: [workgroup][8] phase timestamps of k_sample_part
     int dbg = 0;                // timing experiments only (PT_PART_DBG; results then wrong): bit 0 no run
@@ -136,11 +135,24 @@ constexpr bool for_value(int v, F &&f) {
     return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
 }
 
+// ---- kernels.hip: the dim rule and the score kernels
 // The one dim rule of the single-model path (pt_model_dim_supported): dims 1..512 for every model (both row layouts
 // exist), dims 516..1,024 in multiples of 4 (float4 rows only) for TransE (0) and TransH (1); nothing else
 bool model_dim_supported(int64_t dim, int model);
 // dims at which both row layouts exist (1..512): what the one-float kernels (k_step_sampled, k_lp_scan_t's tile) take
 bool narrow_dim_supported(int64_t dim);
+hipError_t launch_score(const StepParams &P, int mode, const int64_t *h, const int64_t *t, const int64_t *r, int64_t n,
+                        float *out, hipStream_t st);
+hipError_t launch_score_queries(const StepParams &P, int side, const int64_t *qh, const int64_t *qt, const int64_t *qr,
+                                int64_t nq, int64_t E, float *out, hipStream_t st, int global_order = 0);
+// ---- lp.hip: universe link prediction
+// pairs sorted by universe; universe u's pairs are pairs[uoff[2u] .. uoff[2u+1]); uids = the n_active universes with
+// pairs, all of dims that take dim's lane-group shape (pick_shape); base / normal: scratch [n_pairs][ds >= every dim]
+hipError_t launch_lp_min(const LpUniverseDev *us, const LpPair *pairs, int64_t n_pairs, const int64_t *uoff,
+                         const int32_t *uids, int64_t n_active, int64_t dim, int64_t max_ent, int model, int p_norm,
+                         int norm_flag, int64_t global_E, int64_t ds, float *base, float *normal, float *rows,
+                         float *tuple_min, hipStream_t st);
+// ---- sample.hip: the batch samplers
 hipError_t launch_sample(const DeviceGraph &g, const uint64_t *states, int64_t threads, int64_t bs, int64_t neg,
                          int64_t neg_rel, int mode, int bern, int filter, int64_t *h, int64_t *t, int64_t *r, float *y,
                          hipStream_t st);
@@ -148,22 +160,20 @@ hipError_t launch_spin(int64_t us, hipStream_t st);
 hipError_t launch_advance(uint64_t *states, int64_t threads, int64_t bs, int64_t dpp, hipStream_t st);
 hipError_t launch_sample_csr(const DeviceGraph &g, const uint64_t *states, int64_t threads, int64_t bs, int64_t neg,
                              int bern, int filter, int64_t calls, const CsrWork &w, hipStream_t st);
-// one workgroup per call: sampling + LDS counting sort + scan; the streams are NOT advanced (launch_advance).
-// sample_sort_prepare: whether the LDS plan fits for (bs, neg, n) (and the kernel's LDS limit is raised);
-// otherwise use launch_sample_csr + launch_scan_counts
-bool sample_sort_prepare(int64_t bs, int64_t neg, int64_t n, int64_t start_stride);
+// one workgroup per call: sampling + LDS counting sort + scan; the streams are NOT advanced (launch_advance)
 hipError_t launch_sample_sort(const DeviceGraph &g, const uint64_t *states, int64_t threads, int64_t bs, int64_t neg,
                               int bern, int filter, int64_t calls, int64_t n, const CsrWork &w, hipStream_t st);
-// `parts` workgroups per call: sampling + LDS counting sort of each part, call-wide buckets reserved with
-// one atomic per touched count word, the last part of a call scans, the last call advances the streams;
-// off[] holds bucket ranks (the caller sets CsrWork::rank_only for the step kernels).
-// sample_part_fits: whether the LDS plan of `parts` parts per call fits; sample_part_prepare: the same,
-// and raises the kernel's LDS limit (call outside any stream capture)
-bool sample_part_fits(int64_t bs, int64_t neg, int64_t n, int64_t parts);
-bool sample_part_prepare(int64_t bs, int64_t neg, int64_t n, int64_t parts);
+// `parts` workgroups per call: sampling + LDS counting sort of each part, call-wide buckets reserved with one atomic
+// per touched count word, the last part of a call scans, the last call advances the streams; off[] holds bucket
+// ranks (the caller sets CsrWork::rank_only for the step kernels)
 hipError_t launch_sample_part(const DeviceGraph &g, uint64_t *states, int64_t threads, int64_t bs, int64_t neg,
                               int bern, int filter, int64_t calls, int64_t parts, int64_t n, const CsrWork &w,
-                              hipStream_t st, int64_t call0 = 0, int advance = 1);
+                              hipStream_t st);
+// whether a kernel's LDS plan fits (sample_part_fits: with `parts` parts per call); the *_prepare forms also raise the
+// kernel's LDS limit (call outside any stream capture). Where neither fits: launch_sample_csr + launch_scan_counts
+bool sample_sort_prepare(int64_t bs, int64_t neg, int64_t n, int64_t start_stride);
+bool sample_part_fits(int64_t bs, int64_t neg, int64_t n, int64_t parts);
+bool sample_part_prepare(int64_t bs, int64_t neg, int64_t n, int64_t parts);
 hipError_t launch_scan_counts(const CsrWork &w, int64_t n, int64_t calls, uint64_t *states, int64_t threads,
                               int64_t bs, int64_t dpp, hipStream_t st);
 // the raw-buffer kernels (k_step_csr, k_apply_buf) address the ent / rel tables and con_rows contribution rows with
@@ -230,17 +240,6 @@ inline void transd_transfer_pass(const StepParams &P, const StepWorkspace &W, St
     W2->fent = W.fentt; W2->frel = W.frelt;
     W2->lpart = nullptr;
 }
-hipError_t launch_score(const StepParams &P, int mode, const int64_t *h, const int64_t *t, const int64_t *r, int64_t n,
-                        float *out, hipStream_t st);
-hipError_t launch_score_queries(const StepParams &P, int side, const int64_t *qh, const int64_t *qt, const int64_t *qr,
-                                int64_t nq, int64_t E, float *out, hipStream_t st, int global_order = 0);
-// pairs sorted by universe; universe u's pairs are pairs[uoff[2u] .. uoff[2u+1]); uids = the n_active
-// universes with pairs, all of dims that take dim's lane-group shape (pick_shape); base / normal: scratch
-// [n_pairs][ds], ds >= every such dim
-hipError_t launch_lp_min(const LpUniverseDev *us, const LpPair *pairs, int64_t n_pairs, const int64_t *uoff,
-                         const int32_t *uids, int64_t n_active, int64_t dim, int64_t max_ent, int model, int p_norm,
-                         int norm_flag, int64_t global_E, int64_t ds, float *base, float *normal, float *rows,
-                         float *tuple_min, hipStream_t st);
 
 hipError_t launch_torch_init(const pt_torch_init_job *d_jobs, int64_t n, hipStream_t st);
 hipError_t launch_rank_rows(const float *rows, int64_t E, const int64_t *row_of, const int64_t *truth,

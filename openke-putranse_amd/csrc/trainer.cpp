@@ -43,11 +43,6 @@ struct pt_trainer {
     int64_t lpart_cap = 0;                             // W.lpart capacity (positives)
     int device = -1;
     hipStream_t cap = nullptr;
-    // the split sampler's second launch of a chunk (enqueue_sample_split, pt_trainer_sample_csr only): its stream
-    // and the fork / join events
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int64_t split_override = -1;                        // pt_trainer_set_sample_split: head steps, 0 off, -1 auto
     std::map<GraphKey, hipGraphExec_t> graphs;
     int path_override = -1;                             // pt_trainer_set_sampling: PT_PATH_* or -1 (automatic)
     int64_t parts_override = 0;                         // split-sampler workgroups per call (0: automatic)
@@ -73,9 +68,6 @@ struct pt_trainer {
     ~pt_trainer() {
         drop_graphs();
         if (cap) (void)hipStreamDestroy(cap);
-        if (side) (void)hipStreamDestroy(side);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (ev_join) (void)hipEventDestroy(ev_join);
         if (ws_block) (void)hipFree(ws_block);
         if (csr_block) (void)hipFree(csr_block);
         if (csr.prof) (void)hipFree(csr.prof);
@@ -152,9 +144,6 @@ extern "C" int pt_trainer_create(const pt_model_desc *m, pt_trainer **out) {
         t->W.frelt = (int *)b;
     }
     PT_HIP(hipStreamCreateWithFlags(&t->cap, hipStreamNonBlocking));
-    PT_HIP(hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking));
-    PT_HIP(hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming));
-    PT_HIP(hipEventCreateWithFlags(&t->ev_join, hipEventDisableTiming));
     *out = t.release();
     return PT_OK;
 }
@@ -338,35 +327,6 @@ static int enqueue_sample_chunk(pt_trainer *t, pt_sampler *s, pt::CsrWork &w, in
         PT_TIMED(0, pt::launch_sample_csr(dg, s->d_states, s->threads, bs, neg, (int)bern, (int)filter, calls, w, st));
         PT_TIMED(1, pt::launch_scan_counts(w, t->P.ent_total, calls, s->d_states, s->threads, bs, dpp, st));
     }
-    return PT_OK;
-}
-
-// A split-sampler chunk in two launches: the first `head` calls on `st`, the rest on the trainer's side stream
-// forked from `st` after it (neither launch advances the streams: join_sample_split does, after both). What is
-// left of the two-launch split sampling, which training runs no longer use (measured slower):
-// pt_trainer_sample_csr alone takes it, after pt_trainer_set_sample_split.
-static int enqueue_sample_split(pt_trainer *t, pt_sampler *s, pt::CsrWork &w, int64_t bs, int64_t neg, int64_t bern,
-                                int64_t filter, int64_t calls, int64_t head, hipStream_t st) {
-    const pt::DeviceGraph dg = s->g->dev;
-    t->last_path = PT_PATH_PART;
-    w.rank_only = 1;
-    const int64_t parts = part_count(t, calls, bs);
-    pt::CsrWork w0 = w, w1 = pt::csr_view(w, head, bs, neg);
-    w0.prof = w1.prof = nullptr;
-    w1.tick = w.tick + head;
-    PT_HIP(pt::launch_sample_part(dg, s->d_states, s->threads, bs, neg, (int)bern, (int)filter, head, parts,
-                                  t->P.ent_total, w0, st, 0, 0));
-    PT_HIP(hipEventRecord(t->ev_fork, st));
-    PT_HIP(hipStreamWaitEvent(t->side, t->ev_fork, 0));
-    PT_HIP(pt::launch_sample_part(dg, s->d_states, s->threads, bs, neg, (int)bern, (int)filter, calls - head, parts,
-                                  t->P.ent_total, w1, t->side, head, 0));
-    PT_HIP(hipEventRecord(t->ev_join, t->side));
-    return PT_OK;
-}
-// `st` waits for the side launch of enqueue_sample_split, then the streams advance past the chunk's draws
-static int join_sample_split(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, int64_t calls, hipStream_t st) {
-    PT_HIP(hipStreamWaitEvent(st, t->ev_join, 0));
-    PT_HIP(pt::launch_advance(s->d_states, s->threads, bs, (1 + 2 * neg) * calls, st));
     return PT_OK;
 }
 
@@ -572,13 +532,6 @@ extern "C" int pt_trainer_set_sampling(pt_trainer *t, int32_t path, int64_t part
     t->path_override = path;
     t->parts_override = parts;
     t->drop_graphs();   // captured epochs hold the previous choice
-    return PT_OK;
-}
-
-extern "C" int pt_trainer_set_sample_split(pt_trainer *t, int64_t head) {
-    PT_CHECK(t, PT_EINVAL, "null trainer");
-    PT_CHECK(head >= -1, PT_EINVAL, "head must be >= -1");
-    t->split_override = head;   // read by pt_trainer_sample_csr only: captured epochs do not depend on it
     return PT_OK;
 }
 
@@ -808,9 +761,9 @@ extern "C" int pt_trainer_run_timed(pt_trainer *t, pt_sampler *s, int64_t bs, in
     return PT_OK;
 }
 
-// Shims of the removed fused step + apply and slot-scale mode (opt-in modes measured slower than the k_step_csr +
-// k_apply_buf pair), kept for callers that switch them off or ask whether they ran: 0 is accepted,
-// anything else is PT_ENOTSUP, and the getters report 0
+// Shims of the removed fused step + apply, slot-scale mode and two-launch split sampling (opt-in modes measured
+// slower), kept for callers that switch them off or ask whether they ran: off (0; for the split also
+// -1, its former automatic) is accepted, on is PT_ENOTSUP, and the getters report 0
 extern "C" int pt_trainer_set_step_apply(pt_trainer *t, int32_t on) {
     PT_CHECK(t, PT_EINVAL, "null trainer");
     PT_CHECK(!on, PT_ENOTSUP,
@@ -826,6 +779,14 @@ extern "C" int pt_trainer_set_slot_scale(pt_trainer *t, int32_t on) {
     return PT_OK;
 }
 extern "C" int pt_trainer_slot_scale(const pt_trainer *) { return 0; }
+
+extern "C" int pt_trainer_set_sample_split(pt_trainer *t, int64_t head) {
+    PT_CHECK(t, PT_EINVAL, "null trainer");
+    PT_CHECK(head >= -1, PT_EINVAL, "head must be >= -1");
+    PT_CHECK(head <= 0, PT_ENOTSUP,
+             "pt_trainer_set_sample_split: the two-launch split sampling was removed (measured slower, DESIGN.md §4)");
+    return PT_OK;
+}
 
 extern "C" int pt_trainer_last_path(const pt_trainer *t) { return t ? t->last_path : -1; }
 
@@ -847,14 +808,7 @@ extern "C" int pt_trainer_sample_csr(pt_trainer *t, pt_sampler *s, int64_t bs, i
         PT_CHECK(t->csr_part && pt::sample_part_fits(bs, neg, t->P.ent_total, part_count(t, calls, bs)), PT_ENOTSUP,
                  "split sampling plan does not fit LDS");
     hipStream_t st = (hipStream_t)stream;
-    const int64_t head = path == PT_PATH_PART && t->split_override > 0 && t->split_override < calls ? t->split_override
-                                                                                                    : 0;
-    if (head) {   // the split pair (pt_trainer_set_sample_split), joined before the copies
-        rc = enqueue_sample_split(t, s, t->csr, bs, neg, bern, filter, calls, head, st);
-        if (!rc) rc = join_sample_split(t, s, bs, neg, calls, st);
-    } else {
-        rc = enqueue_sample_chunk(t, s, t->csr, bs, neg, bern, filter, calls, path, st, nullptr);
-    }
+    rc = enqueue_sample_chunk(t, s, t->csr, bs, neg, bern, filter, calls, path, st, nullptr);
     if (rc) return rc;
     const pt::CsrWork &w = t->csr;
     const int64_t E = t->P.ent_total, slots = bs * neg;

@@ -1,4 +1,4 @@
-// What capi.cpp and the trainer runtime (trainer.cpp) share: the sampler object and the model descriptor check.
+// What capi.cpp, legacy.cpp and the trainer runtime (trainer.cpp) share: the sampler object and the model descriptor check.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -19,7 +19,8 @@ Shapes follow the reference's step: the k-th negative of positive b is slot b*ne
 multiple of the 1024/512-thread strides nor divided by neg (bs 200, neg 13: the second lock-step slot,
 the incremental (b, k) carry), neg > 1024 (db == 0), filter = 0 and bern = 0, bs*neg >= 65536 (the
 split sampler's unpacked 32-bit counts), and short chunks (6, 9 and 20 calls: the split sampler's automatic part
-counts).
+counts). Every chunk is sampled by one launch of its path; the setters of the removed modes (fused step + apply,
+slot scale, two-launch split sampling) are checked as shims.
 """
 import ctypes
 
@@ -156,27 +157,21 @@ def test_split_sampler_any_part_count(parts):
         ctx.close()
 
 
-@pytest.mark.parametrize("head", [1, 2, 7])
-@pytest.mark.parametrize("case", [(200, 13, 1, 1, 20, 17), (3000, 25, 1, 1, 6, 19), (200, 13, 0, 0, 9, 23)],
-                         ids=lambda c: "bs%d-neg%d-bern%d-filter%d-calls%d" % c[:5])
-def test_split_sampler_two_launches(case, head):
-    """A chunk sampled by two k_sample_part launches side by side (pt_trainer_set_sample_split: the first `head`
-    calls on the caller's stream, the rest on the trainer's side stream, the streams advanced after both):
-    the same batches as the oracle, and the streams end past exactly `calls` calls."""
-    bs, neg, bern, filt, calls, seed = case
+def test_removed_sample_split_shim():
+    """The two-launch split sampling was removed; its setter stays as a shim on a live trainer:
+    heads 0 and -1 (off) are accepted, a head > 0 is PT_ENOTSUP (6) with a message that says so, and a PT_PATH_PART
+    chunk sampled afterwards still equals the oracle."""
+    bs, neg, bern, filt, calls, seed = 200, 13, 0, 0, 9, 23
     want, E = _oracle_batches(seed, bs, neg, bern, filt, calls)
     ctx = _Ctx(seed)
-    ctx.n.check(ctx.L.pt_trainer_set_sample_split(ctx.t, head))
     try:
+        for head in (0, -1):
+            assert ctx.L.pt_trainer_set_sample_split(ctx.t, head) == 0
+        for head in (1, 7):
+            assert ctx.L.pt_trainer_set_sample_split(ctx.t, head) == 6
+            msg = ctx.L.pt_last_error().decode()
+            assert "removed" in msg and "DESIGN" in msg, msg
         _check_batches(ctx.sample(bs, neg, bern, filt, calls, PATHS["part"]), want, E, bs, neg)
-        kg = oracle.KG.load(KG_SMALL)
-        st = oracle.GlibcRand(seed).rand_reset(THREADS)
-        for _ in range(calls):
-            kg.sample(st, THREADS, bs, neg, bern, filt)
-        nxt = ctx.sample(bs, neg, bern, filt, 1, PATHS["part"])
-        h, t, r, _ = kg.sample(st, THREADS, bs, neg, bern, filt)
-        np.testing.assert_array_equal(nxt[0][0][:, 0], h[:bs].astype(np.int32))
-        np.testing.assert_array_equal(nxt[0][0][:, 2], t[:bs].astype(np.int32))
     finally:
         ctx.close()
 

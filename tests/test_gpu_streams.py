@@ -5,7 +5,7 @@ over its share of the CUs (pt_universe_set_create). Round 4 launched them on the
 streams: in a process that already held streams (torch's, the C2 trainer's capture stream) two class launches
 shared one of the process's GPU_MAX_HW_QUEUES hardware queues and ran one after the other (the driver's default
 bench line: C3 58.7 ms against 35.7 ms standalone). The launches now run on process-wide streams with hardware
-queues of their own (class_streams, capi.cpp). This test holds a stream of its own, trains a four-launch set and
+queues of their own (class_streams, universe_set.cpp). This test holds a stream of its own, trains a four-launch set and
 checks from pt_universe_set_launch_times that every launch started before any other finished. The trained tables
 are checked elsewhere (test_gpu_pu.py, test_gpu_configs.py); here only the schedule."""
 import ctypes
