@@ -282,9 +282,8 @@ int pt_universe_set_free(pt_universe_set *s);
  * step count, batch size, dim and entity count (last train call); out[.][7]: the universe's start on the 100 MHz
  * wall clock (low 32 bits, in the high word) and its duration in those ticks (low word); out[.][63]: where it ran -
  * its XCD (high word) and the workgroup's HW_REG_HW_ID (low word: CU, SH, SE fields); out[.][60..62]
- * (the removed team universes' width, barrier cycles and phase-B rows) stay in the layout and stay zero; the
- * other words of out[.][8..59]: phase stamps of one step of lane group 0 in the measurement build (make TUNING=1),
- * zero otherwise */
+ * (the removed team universes' width, barrier cycles and phase-B rows) and out[.][8..59] (the removed measurement
+ * build's phase stamps of one step) stay in the layout, reserved and zero */
 int pt_universe_set_profiling(pt_universe_set *s, int32_t on);
 /* Compatibility shim: team universes (teams of 2 or 4 workgroups training one universe) measured slower than one
  * workgroup at every width and were removed; every universe trains on one workgroup. The setter

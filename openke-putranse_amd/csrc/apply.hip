@@ -13,9 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdlib>
 
-#include "tuning.h"
 #include "device.h"
 #include "graph.h"
 #include "kernels.h"
@@ -47,7 +45,6 @@ struct ApplyParams {
     float *loss;
     const float *lpart;   // [bs] per-positive loss partials of the step
     float margin, inv_count;
-    int dbg;   // timing experiments only (PT_STEP_DBG bit 3: contribution rows read from a 4096-row hot window)
     int loss_assign;
 };
 
@@ -197,9 +194,7 @@ __global__ __launch_bounds__(256) void k_apply_buf(ApplyParams A) {
         Vec c[NC];
 #pragma unroll
         for (int q = 0; q < NC; ++q)
-            bload(c[q], c_rs,
-                  c0 + j + q < c1 ? (uint32_t)(PT_ABLATE(A.dbg, 8) ? (c0 + j + q) & 4095 : c0 + j + q) * rowb : kOob, D,
-                  lane);
+            bload(c[q], c_rs, c0 + j + q < c1 ? (uint32_t)(c0 + j + q) * rowb : kOob, D, lane);
 #pragma unroll
         for (int q = 0; q < NC; ++q)
 #pragma unroll
@@ -264,7 +259,6 @@ hipError_t launch_apply(const StepParams &P, const StepWorkspace &W, uint64_t *s
     A.lpart = W.lpart;
     A.margin = P.margin;
     A.inv_count = P.inv_count;
-    A.dbg = P.dbg;
     A.loss_assign = P.loss_assign;
     int64_t rows = 0;
     for (int i = 0; i < A.ntab; ++i) rows += A.t[i].rows;

@@ -4,12 +4,10 @@
 // pt_universes_train, is universe_set.cpp; the reference's Base.so symbols are legacy.cpp.)
 #include <algorithm>
 #include <atomic>
-#include <cstdlib>
 #include <string>
 #include <thread>
 #include <vector>
 
-#include "tuning.h"
 #include "common.h"
 #include "graph.h"
 #include "kernels.h"
@@ -67,7 +65,6 @@ int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
         P.ent_t = m->ent_transfer; P.rel_t = m->rel_transfer;
         P.ent_t_acc = m->ent_transfer_acc; P.rel_t_acc = m->rel_transfer_acc;
     }
-    if (const char *v = pt_tuning_env("PT_STEP_DBG")) P.dbg = atoi(v);
     return PT_OK;
 }
 
@@ -328,10 +325,9 @@ extern "C" int pt_torch_init_tables(const pt_torch_init_job *jobs, int64_t n, vo
 
 // ======================================================================== link prediction =======
 // keys of one batch of pt_lp_min_scores: as many score rows (global_ent_total floats each) as fit the batch
-// budget (PT_LP_BATCH_MB in the tuning build, default 192), at least one
+// budget of 192 MB, at least one
 static int64_t lp_keys_per_batch(int64_t global_ent_total) {
-    int64_t batch_mb = 192;
-    if (const char *v = pt_tuning_env("PT_LP_BATCH_MB")) batch_mb = std::max<int64_t>(1, atoll(v));
+    const int64_t batch_mb = 192;
     return std::max<int64_t>(1, (batch_mb << 20) / (4 * std::max<int64_t>(global_ent_total, 1)));
 }
 extern "C" int64_t pt_lp_keys_per_batch(int64_t global_ent_total) { return lp_keys_per_batch(global_ent_total); }
@@ -365,7 +361,7 @@ extern "C" int pt_lp_min_scores(const pt_lp_universe *us, int64_t n_universes, i
     // Jobs = (lane-group row shape of the universes' dims, key batch): one launch pair per job covers every
     // dim of that shape (C3's ~80 dims take ~10 shapes: one launch pair per dim left most of the GPU idle). A
     // key batch's score rows (keys x global_ent_total floats) are sized to stay resident in the Infinity
-    // Cache while its pairs' atomicMins land (PT_LP_BATCH_MB, default 192); inside a job the pairs are
+    // Cache while its pairs' atomicMins land (lp_keys_per_batch's 192 MB); inside a job the pairs are
     // sorted by universe so each universe's entity rows are read once per job.
     int64_t n_keys = 0;
     for (int64_t i = 0; i < n_pairs; ++i) n_keys = std::max<int64_t>(n_keys, (int64_t)pairs[i].key + 1);

@@ -18,8 +18,6 @@ struct StepParams {
     int64_t batch_size, neg;
     float inv_count;   // 1 / (batch_size * neg)
     int loss_assign = 0;   // the apply pass stores the step's loss (=) instead of adding it (+=)
-    int dbg = 0;       // timing experiments only (PT_STEP_DBG): bit 0 skip corrupted-row stores, bit 1 skip
-                       // positive-row atomics, bit 2 skip negative row loads (results are then wrong)
     // TransD (model 2): ent_transfer / rel_transfer and their Adagrad state (appended: the fields above keep their
     // places in the argument blocks of the TransE / TransH kernels)
     float *ent_t = nullptr, *rel_t = nullptr;
@@ -51,9 +49,6 @@ struct CsrWork {
     float *contrib = nullptr;   // [bs*neg][dim] gradient rows of the corrupted entities (one step)
     int32_t *tick = nullptr;    // [calls + 1] parts of a call done, then calls done (k_sample_part; zero between uses)
     int rank_only = 0;          // off[] holds bucket ranks (k_sample_part) instead of destinations
-    uint64_t *prof = nullptr;   // PT_PART_PROF=1 only: [workgroup][8] phase timestamps of k_sample_part
-    int dbg = 0;                // timing experiments only (PT_PART_DBG; results then wrong): bit 0 no run
-                                // search, bit 1 no stream jump, bit 2 no 64-bit modulo
     int64_t cnt_stride = 0, start_stride = 0;
 };
 

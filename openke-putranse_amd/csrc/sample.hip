@@ -6,7 +6,6 @@
 
 #include <cstdint>
 
-#include "tuning.h"
 #include "device.h"
 #include "graph.h"
 #include "kernels.h"
@@ -129,12 +128,11 @@ __device__ __forceinline__ void jump_tab_fill(Affine *jt, int64_t neg, int tid) 
 }
 
 __device__ __forceinline__ SlotDraw slot_prepare(const int32_t *q, int32_t k, int64_t E, int filter,
-                                                 const DeviceGraph &g, const Affine *jt, int dbg = 0) {
+                                                 const DeviceGraph &g, const Affine *jt) {
     SlotDraw d;
     const uint64_t s1 = *reinterpret_cast<const uint64_t *>(q + 10);
     uint64_t s;
-    if (PT_ABLATE(dbg, 2)) s = s1 + k;
-    else if (k < kJumpTab) { const Affine m = jt[k]; s = m.a * s1 + m.c; }
+    if (k < kJumpTab) { const Affine m = jt[k]; s = m.a * s1 + m.c; }
     else s = lcg_jump(s1, (uint64_t)(2 * k));
     d.side = (float)(lcg_next(s) % 1000ULL) < __int_as_float(q[0]) ? 1 : 0;
     d.search = false;
@@ -144,10 +142,9 @@ __device__ __forceinline__ SlotDraw slot_prepare(const int32_t *q, int32_t k, in
         const int32_t *vals = d.side ? g.head_t : g.tail_h;
         const int32_t lo = d.side ? q[1] : q[3], hi = d.side ? q[2] : q[4];
         const int32_t vlo = d.side ? q[5] : q[7], vhi = d.side ? q[6] : q[8];
-        const int64_t tmp = PT_ABLATE(dbg, 4) ? (int64_t)((uint32_t)lcg_next(s) & 8191) : rand_max(s, E - (hi - lo + 1));
+        const int64_t tmp = rand_max(s, E - (hi - lo + 1));
         if (tmp < vlo) d.e = tmp;
         else if (tmp > vhi - hi + lo - 1) d.e = tmp + hi - lo + 1;
-        else if (PT_ABLATE(dbg, 1)) d.e = tmp;
         else { d.search = true; d.q = run_search(vals, lo, hi, vlo, vhi, (int32_t)tmp); d.e = 0; }
     } else {
         const int64_t tmp = rand_max(s, E - 1);
@@ -326,9 +323,6 @@ __global__ __launch_bounds__(NT) void k_sample_part(DeviceGraph g, uint64_t *__r
     const int64_t b0 = part * bs / parts, b1 = (part + 1) * bs / parts;
     const int64_t E = g.ent_total;
     const int64_t cwords = PACK ? (E + 1) >> 1 : E;
-    uint64_t *prof = w.prof ? w.prof + 8 * (int64_t)blockIdx.x : nullptr;
-#define PT_PHASE(i) if (prof && tid == 0) prof[i] = wall_clock64()
-    PT_PHASE(0);
     Affine *jt = reinterpret_cast<Affine *>(lds);        // [jump_tab_len(neg)] jump maps
     int32_t *cnt = lds + 4 * jump_tab_len(neg);
     int32_t *pi = cnt + ((cwords + 3) & ~int64_t(3));    // [b1 - b0][12] positive records (k_sample_sort)
@@ -350,7 +344,6 @@ __global__ __launch_bounds__(NT) void k_sample_part(DeviceGraph g, uint64_t *__r
         w.pos[call * bs + b] = make_int4((int)pd.h, (int)pd.r, (int)pd.t, 0);
     }
     __syncthreads();
-    PT_PHASE(1);
     const int64_t slots = bs * neg;
     int32_t *nrec = w.neg + call * slots;
     int32_t *noff = w.off + call * slots;
@@ -372,7 +365,7 @@ __global__ __launch_bounds__(NT) void k_sample_part(DeviceGraph g, uint64_t *__r
 #pragma unroll
         for (int i = 0; i < SL; ++i) {
             const bool live = o + i * NT < o1;
-            d[i] = slot_prepare(pi + 12 * (live ? bi : b), live ? ki : k, E, filter, g, jt, w.dbg);
+            d[i] = slot_prepare(pi + 12 * (live ? bi : b), live ? ki : k, E, filter, g, jt);
             if (!live) { d[i].q.l = 0; d[i].q.r = 1; d[i].search = false; }
             bi += db; ki += dk;
             if (ki >= neg32) { ki -= neg32; ++bi; }
@@ -394,7 +387,6 @@ __global__ __launch_bounds__(NT) void k_sample_part(DeviceGraph g, uint64_t *__r
         b = bi; k = ki;
     }
     __syncthreads();
-    PT_PHASE(2);
     // reserve this part's range in every touched call-wide bucket with one returning atomic per count
     // word (packed: the call's global counts are packed the same way, each half < 65536, so one add
     // reserves both buckets); the LDS word becomes the bases. Batches of 8 words per thread keep the
@@ -414,7 +406,6 @@ __global__ __launch_bounds__(NT) void k_sample_part(DeviceGraph g, uint64_t *__r
             if (v[u]) cnt[i0 + u * NT] = r[u];
     }
     __syncthreads();
-    PT_PHASE(3);
     // rank inside the call-wide bucket: from registers, or re-read (same thread, same addresses)
     if (one) {
 #pragma unroll
@@ -434,8 +425,6 @@ __global__ __launch_bounds__(NT) void k_sample_part(DeviceGraph g, uint64_t *__r
     __syncthreads();
     if (tid == 0) is_last = agent_add(&w.tick[call], 1) == (int32_t)(parts - 1);
     __syncthreads();
-    PT_PHASE(4);
-    if (prof && tid == 0) prof[7] = is_last;
     if (!is_last) return;
     if (tid == 0) w.tick[call] = 0;   // plain store: read again only by a later launch (kernel boundary)
     // last part: the call's bucket sizes, exchanged with zeros (atomics on both sides: every part's adds
@@ -449,7 +438,6 @@ __global__ __launch_bounds__(NT) void k_sample_part(DeviceGraph g, uint64_t *__r
             if (i0 + u * NT < cwords) cnt[i0 + u * NT] = r[u];
     }
     __syncthreads();
-    PT_PHASE(5);
     // exclusive scan over the entities into start[]: contiguous words per thread, wave shuffles, LDS
     // wave totals (k_sample_sort's scan on the packed or plain words)
     int32_t *start = w.start + call * w.start_stride;
@@ -483,8 +471,6 @@ __global__ __launch_bounds__(NT) void k_sample_part(DeviceGraph g, uint64_t *__r
         }
     }
     if (tid == NT - 1) start[E] = run;   // the last thread's chunk ends at the end (or is empty): run = total
-    PT_PHASE(6);
-#undef PT_PHASE
     // the last call's last part advances the sampler streams past every call's draws: every part of every
     // call read them (positive draws) before its count atomics and tickets
     __syncthreads();

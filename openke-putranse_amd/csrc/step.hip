@@ -14,9 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdlib>
 
-#include "tuning.h"
 #include "device.h"
 #include "graph.h"
 #include "kernels.h"
@@ -151,7 +149,7 @@ __global__ __launch_bounds__(256) void k_step_sampled(StepParams P, DeviceGraph 
         auto load_chunk = [&](Vec(&E)[NCH], int64_t c0) {
 #pragma unroll
             for (int k = 0; k < NCH; ++k)
-                if (c0 + k < k_hi && !PT_ABLATE(P.dbg, 4)) vload(E[k], P.ent + (mine[c0 + k] >> 1) * D, D, lane);
+                if (c0 + k < k_hi) vload(E[k], P.ent + (mine[c0 + k] >> 1) * D, D, lane);
         };
         load_chunk(EA, k_lo);
         // ---- positive forward
@@ -219,11 +217,7 @@ __global__ __launch_bounds__(256) void k_step_sampled(StepParams P, DeviceGraph 
                     gs.x[i] = tail_side ? -gk.x[i] : gk.x[i];   // corrupted tail gets -g, corrupted head +g
                 }
                 if constexpr (MODEL == 0) {
-                    if constexpr (CSR) {
-                        if (!PT_ABLATE(P.dbg, 1)) vstore(gs, dst, D, lane);
-                    } else {
-                        sink.ent(e, gs, D, lane);
-                    }
+                    if constexpr (CSR) vstore(gs, dst, D, lane); else sink.ent(e, gs, D, lane);
                 } else {
                     Vec gp, ge;
                     if (nf) vnormalize_bwd<true>(Es, en, gs, gp); else gp = gs;
@@ -290,11 +284,9 @@ __global__ __launch_bounds__(256) void k_step_sampled(StepParams P, DeviceGraph 
             aT.x[i] -= gv.x[i];
         }
         if constexpr (MODEL == 0) {
-            if (!PT_ABLATE(P.dbg, 2)) {
-                sink.rel(rp, aR, D, lane);
-                sink.ent(hp, aH, D, lane);
-                sink.ent(tp, aT, D, lane);
-            }
+            sink.rel(rp, aR, D, lane);
+            sink.ent(hp, aH, D, lane);
+            sink.ent(tp, aT, D, lane);
         } else {
             sink.rel(rp, aR, D, lane);
 #pragma unroll
@@ -389,7 +381,7 @@ __global__ __launch_bounds__(NT) void k_step_csr(StepParams P, GlobalSink sink, 
             for (int u = 0; u < NCH; ++u) {
                 const int kk = k0 + u < wend ? k0 + u : wend - 1;
                 const uint32_t e = (uint32_t)(gbcast<G>(rec, kk - w0) >> 1);
-                bload(E[u], ent_rs, PT_ABLATE(P.dbg, 4) ? kOob : e * rowb, D, lane);
+                bload(E[u], ent_rs, e * rowb, D, lane);
             }
         };
         if (w0 < wend) load_chunk(EA, w0);
@@ -433,7 +425,7 @@ __global__ __launch_bounds__(NT) void k_step_csr(StepParams P, GlobalSink sink, 
                 // slot gradient d loss / d e-hat: -g for a corrupted tail, +g for a corrupted head
                 // (g = dL/dv); an inactive pair stores zeros (the reserved slot must be defined)
                 vpnorm_bwd<true>(vk, ns, p, tail_side ? c : -c, gs);
-                bstore(gs, con_rs, PT_ABLATE(P.dbg, 1) ? kOob : slot, D, lane);
+                bstore(gs, con_rs, slot, D, lane);
                 if (tail_side) {
 #pragma unroll
                     for (int i = 0; i < Vec::N; ++i) At.x[i] -= gs.x[i];
@@ -498,7 +490,7 @@ __global__ __launch_bounds__(NT) void k_step_csr(StepParams P, GlobalSink sink, 
     }
     if (!active) return;
     if (lane == 0 && sink.lpart) sink.lpart[b] = lsum;
-    if (uni<G>(csum) == 0.f || PT_ABLATE(P.dbg, 2)) return;   // no active pair: every accumulator is zero
+    if (uni<G>(csum) == 0.f) return;   // no active pair: every accumulator is zero
     Vec gv, aH, aR, aT, vpos;
 #pragma unroll
     for (int i = 0; i < Vec::N; ++i) vpos.x[i] = bt.x[i] - th.x[i];
@@ -633,18 +625,6 @@ hipError_t launch_step(const StepParams &P, const DeviceGraph &g, const uint64_t
                     for_value<1, 2>(P.p_norm == 1 ? 1 : 2, [&](auto pn) {
                         constexpr int SG = sv.value * T::G, NT = SG >= 256 || 256 % SG != 0 ? SG : 256;
                         const dim3 grid((unsigned)((P.batch_size * SG + NT - 1) / NT)), block(NT);
-#ifdef PT_TUNING
-                        // PT_CSR_NCH=1|2: the chunk depth of the wide shapes, for the A/B timing behind csr_nch
-                        if constexpr (T::KCH > 2) {
-                            const char *v = pt_tuning_env("PT_CSR_NCH");
-                            const bool forced = v && for_value<1, 2>(atoi(v), [&](auto n) {
-                                hipLaunchKernelGGL((dev::k_step_csr<T::G, 4, T::KCH, n.value, sv.value, pn.value, NT>),
-                                                   grid, block, 0, st, P, sink, *csr);
-                                e = hipGetLastError();
-                            });
-                            if (forced) return;
-                        }
-#endif
                         constexpr int NCH = csr_nch(T::KCH, sv.value);
                         hipLaunchKernelGGL((dev::k_step_csr<T::G, 4, T::KCH, NCH, sv.value, pn.value, NT>), grid, block,
                                            0, st, P, sink, *csr);

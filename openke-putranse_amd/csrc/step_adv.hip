@@ -18,17 +18,12 @@
 // trainer's gradient rows plus touched flags (row_atomic below). A negative that shares the positive's relation and
 // one entity (every cross-sampled negative, and every normal-mode entity corruption) costs one row load per pass:
 // h^ + r^ and t^ stay in registers. Rows of NCH negatives are in flight together. Pass 2 re-reads the rows it needs
-// (K x dim x 4 bytes per positive: L2-sized). STAGE = true (measurement build only, PT_ADV_STAGE=1) is the alternative
-// that was measured against it: pass 1 keeps the raw rows of a group's negatives in LDS and pass 2 reads them there
-// (K x dim x 4 bytes of LDS per positive: one positive per CU at K = 64, dim = 512). It is slower (DESIGN.md
-// section 4), so the product build does not instantiate it.
+// (K x dim x 4 bytes per positive: L2-sized); a pass 2 that read them from rows staged in LDS by pass 1 was measured
+// slower.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdint>
-#include <cstdlib>
 
-#include "tuning.h"
 #include "device.h"
 #include "kernels.h"
 
@@ -63,15 +58,13 @@ struct AdvSink {   // (row_atomic: device.h)
     }
 };
 
-template <int G, int VEC, int KCH, int NCH, bool STAGE = false>
+template <int G, int VEC, int KCH, int NCH>
 __global__ __launch_bounds__(256) void k_step_adv(StepParams P, LossParams L, const int64_t *__restrict__ bh,
                                                   const int64_t *__restrict__ bt, const int64_t *__restrict__ br,
                                                   AdvSink sink, float *__restrict__ lpart) {
     using Vec = V<G, VEC, KCH>;
-    static_assert(!STAGE || VEC == 4, "the staged variant exists for float4 rows");
     constexpr int RW = VEC == 4 ? KCH * G * VEC : 0;   // floats of a group's transpose row (row_atomic)
-    // [groups per block][RW] transpose rows, then [groups per block][neg] scores (STAGE: then [groups per block]
-    // [neg][RW] staged rows, each lane writing and reading its own float4 chunks)
+    // [groups per block][RW] transpose rows, then [groups per block][neg] scores
     extern __shared__ __attribute__((aligned(16))) float s_lds[];
     const int gpb = (int)blockDim.x / G;
     const int lane = threadIdx.x % G;
@@ -82,7 +75,6 @@ __global__ __launch_bounds__(256) void k_step_adv(StepParams P, LossParams L, co
     if (b >= bs) return;   // (no block-wide barrier below: a group is inside one wave)
     float *tb = s_lds + (size_t)grp * RW;
     float *sc = s_lds + (size_t)gpb * RW + (size_t)grp * neg;
-    float *stage = s_lds + (size_t)gpb * (RW + neg) + (size_t)grp * neg * RW;
     const int D = (int)P.dim;
     const int p = P.p_norm;
     const bool nf = P.norm_flag != 0;
@@ -132,28 +124,13 @@ __global__ __launch_bounds__(256) void k_step_adv(StepParams P, LossParams L, co
                 const int64_t o = (int64_t)(c0 + u + 1) * bs + b;
                 hk[u] = bh[o]; tk[u] = bt[o]; rk[u] = br[o];
                 kind[u] = rk[u] != rp ? 2 : (hk[u] == hp ? 0 : (tk[u] == tp ? 1 : 2));
-                if (kind[u] < 2 && !(STAGE && pass == 1))
-                    vload(E[u], P.ent + (kind[u] == 0 ? tk[u] : hk[u]) * D, D, lane);
+                if (kind[u] < 2) vload(E[u], P.ent + (kind[u] == 0 ? tk[u] : hk[u]) * D, D, lane);
             }
 #pragma unroll
             for (int u = 0; u < NCH; ++u) {
                 if (kind[u] < 0) continue;
                 Vec vk;
                 if (kind[u] < 2) {
-                    if constexpr (STAGE) {
-                        float4 *sr = reinterpret_cast<float4 *>(stage + (size_t)(c0 + u) * RW);
-#pragma unroll
-                        for (int k = 0; k < KCH; ++k) {
-                            if (pass == 0) {
-                                sr[k * G + lane] = make_float4(E[u].x[k * 4 + 0], E[u].x[k * 4 + 1],
-                                                               E[u].x[k * 4 + 2], E[u].x[k * 4 + 3]);
-                            } else {
-                                const float4 f = sr[k * G + lane];
-                                E[u].x[k * 4 + 0] = f.x; E[u].x[k * 4 + 1] = f.y;
-                                E[u].x[k * 4 + 2] = f.z; E[u].x[k * 4 + 3] = f.w;
-                            }
-                        }
-                    }
                     Vec eh;
                     if (nf) vnormalize(E[u], eh); else eh = E[u];
                     if (kind[u] == 0) {
@@ -303,47 +280,11 @@ hipError_t launch_step_adv(const StepParams &P, const LossParams &L, const int64
     const int64_t cap = kAdvLdsFloats / (P.neg + rw);
     if (gpb > cap) gpb = cap;
     dev::AdvSink sink{W.gent, W.grel, W.fent, W.frel};
-#ifdef PT_TUNING
-    // PT_ADV_STAGE=1: the LDS-staged pass 2 (float4 rows), as many groups per block as 160 KB of LDS hold
-    if (const char *v = pt_tuning_env("PT_ADV_STAGE")) {
-        const int64_t per = P.neg + rw + P.neg * rw, lim = 160 * 1024 / 4;
-        if (atoi(v) != 0 && s.VEC == 4 && per <= lim && P.neg % 4 == 0) {   // (float4-aligned staged rows)
-            const int64_t g2 = std::min<int64_t>(256 / s.G, lim / per);
-            const dim3 grid2((unsigned)((P.batch_size + g2 - 1) / g2)), block2((unsigned)(g2 * s.G));
-            const size_t lds2 = sizeof(float) * (size_t)(g2 * per);
-            hipError_t e = hipErrorInvalidValue;
-            const bool staged = for_shape(s, [&](auto sh) {
-                using T = decltype(sh);
-                if constexpr (T::VEC == 4) {
-                    auto kern = dev::k_step_adv<T::G, 4, T::KCH, 4, true>;
-                    e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-                    if (e != hipSuccess) return;
-                    hipLaunchKernelGGL(kern, grid2, block2, lds2, st, P, L, bh, bt, br, sink, W.lpart);
-                    e = hipGetLastError();
-                }
-            });
-            if (staged) return e;
-        }
-    }
-#endif
     const dim3 grid((unsigned)((P.batch_size + gpb - 1) / gpb)), block((unsigned)(gpb * s.G));
     const size_t lds = sizeof(float) * (size_t)(gpb * (P.neg + rw));
     hipError_t e = hipErrorInvalidValue;
     for_shape(s, [&](auto sh) {
         using T = decltype(sh);
-#ifdef PT_TUNING
-        // PT_ADV_NCH=1|2|4: the chunk depth of the wide shapes, for the A/B timing behind adv_nch
-        if (const char *v = pt_tuning_env("PT_ADV_NCH")) {
-            if constexpr (T::VEC * T::KCH > 8) {
-                const bool forced = for_value<1, 2, 4>(atoi(v), [&](auto n) {
-                    hipLaunchKernelGGL((dev::k_step_adv<T::G, T::VEC, T::KCH, n.value>), grid, block, lds, st, P, L, bh,
-                                       bt, br, sink, W.lpart);
-                    e = hipGetLastError();
-                });
-                if (forced) return;
-            }
-        }
-#endif
         hipLaunchKernelGGL((dev::k_step_adv<T::G, T::VEC, T::KCH, adv_nch(T::VEC, T::KCH)>), grid, block, lds, st, P, L,
                            bh, bt, br, sink, W.lpart);
         e = hipGetLastError();

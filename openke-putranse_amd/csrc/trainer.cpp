@@ -3,15 +3,12 @@
 // one hipGraph per epoch shape by pt_trainer_run), the measurement hook and the reference-order mode.
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <map>
 #include <memory>
 #include <string>
 #include <tuple>
 #include <vector>
 
-#include "tuning.h"
 #include "common.h"
 #include "graph.h"
 #include "kernels.h"
@@ -46,7 +43,6 @@ struct pt_trainer {
     std::map<GraphKey, hipGraphExec_t> graphs;
     int path_override = -1;                             // pt_trainer_set_sampling: PT_PATH_* or -1 (automatic)
     int64_t parts_override = 0;                         // split-sampler workgroups per call (0: automatic)
-    int64_t prof_calls = 0, prof_parts = 0, prof_cap = 0;   // PT_PART_PROF (tuning build) record layout
     // reference-order (deterministic) mode: ordered.hip's step on k_sample batches (pt_trainer_set_deterministic)
     bool ordered = false;
     void *ord_block = nullptr;
@@ -70,7 +66,6 @@ struct pt_trainer {
         if (cap) (void)hipStreamDestroy(cap);
         if (ws_block) (void)hipFree(ws_block);
         if (csr_block) (void)hipFree(csr_block);
-        if (csr.prof) (void)hipFree(csr.prof);
         if (W.lpart) (void)hipFree(W.lpart);
         if (ord_block) (void)hipFree(ord_block);
     }
@@ -78,14 +73,8 @@ struct pt_trainer {
 
 namespace {
 
-// negatives at or above this count take the counting-sort path (PT_CSR=0/1 overrides)
-bool use_csr(int64_t neg) {
-    static int forced = [] {
-        const char *v = pt_tuning_env("PT_CSR");
-        return v ? atoi(v) : -1;
-    }();
-    return forced >= 0 ? forced != 0 : neg >= 4;
-}
+// negatives at or above this count take the counting-sort path
+bool use_csr(int64_t neg) { return neg >= 4; }
 
 // arguments of in-kernel-sampled steps
 int check_step_args(const pt::StepParams &P, pt_sampler *s, int64_t bs, int64_t neg) {
@@ -171,24 +160,10 @@ static const int64_t kSampleSortMinCalls = 96;
 // the split sampler (k_sample_part) runs ceil(kPartTarget / calls) workgroups per call
 static const int64_t kPartTarget = 512;
 
-// Sampling path for a chunk of `calls` steps: pt_trainer_set_sampling forces one (where its plan fits;
-// the tuning build also reads PT_SAMPLE_MODE = fused | part | twopass and PT_SAMPLE_TWO_PASS=1); by default
-// the fused kernel for chunks of >= kSampleSortMinCalls steps, the split sampler below that.
-static int sample_mode(const pt_trainer *t) {
-    if (t->path_override >= 0) return t->path_override;
-    const char *tp = pt_tuning_env("PT_SAMPLE_TWO_PASS");
-    if (tp && atoi(tp) != 0) return PT_PATH_TWO_PASS;
-    const char *v = pt_tuning_env("PT_SAMPLE_MODE");
-    if (!v) return -1;
-    if (!strcmp(v, "fused")) return PT_PATH_FUSED;
-    if (!strcmp(v, "part")) return PT_PATH_PART;
-    if (!strcmp(v, "twopass")) return PT_PATH_TWO_PASS;
-    return -1;
-}
+// Sampling path for a chunk of `calls` steps: pt_trainer_set_sampling forces one (`forced`, where its plan fits); by
+// default the fused kernel for chunks of >= kSampleSortMinCalls steps, the split sampler below that.
 static int64_t part_count(const pt_trainer *t, int64_t calls, int64_t bs) {
-    int64_t p = (kPartTarget + calls - 1) / calls;
-    if (t->parts_override > 0) p = t->parts_override;
-    else if (const char *v = pt_tuning_env("PT_PART_COUNT")) p = atoll(v);
+    int64_t p = t->parts_override > 0 ? t->parts_override : (kPartTarget + calls - 1) / calls;
     if (p < 2) p = 2;
     return p > bs ? bs : p;
 }
@@ -247,14 +222,6 @@ static int ensure_csr(pt_trainer *t, int64_t bs, int64_t neg) {
     // plans fit (sets the kernels' LDS attributes here, outside any stream capture)
     t->csr_fused = pt::sample_sort_prepare(bs, neg, E, ss);
     t->csr_part = pt::sample_part_prepare(bs, neg, E, std::min<int64_t>(bs, kPartTarget));
-    if (const char *dd = pt_tuning_env("PT_PART_DBG")) t->csr.dbg = atoi(dd);
-    // PT_PART_PROF=1: phase timestamps of the split sampler (reported by pt_trainer_run_timed)
-    if (const char *pp = pt_tuning_env("PT_PART_PROF")) {
-        if (atoi(pp) != 0 && !t->csr.prof) {
-            t->prof_cap = kCsrChunk * 1024;   // (call, part) records
-            PT_HIP(hipMalloc(&t->csr.prof, sizeof(uint64_t) * 8 * (size_t)t->prof_cap));
-        }
-    }
     return PT_OK;
 }
 
@@ -315,14 +282,8 @@ static int enqueue_sample_chunk(pt_trainer *t, pt_sampler *s, pt::CsrWork &w, in
         PT_TIMED(1, pt::launch_advance(s->d_states, s->threads, bs, dpp * calls, st));
     } else if (path == PT_PATH_PART) {
         const int64_t parts = part_count(t, calls, bs);
-        pt::CsrWork wp = w;
-        if (wp.prof && calls * parts > t->prof_cap) wp.prof = nullptr;   // record only what the buffer holds
-        if (wp.prof) {
-            t->prof_calls = calls;
-            t->prof_parts = parts;
-        }
         PT_TIMED(0, pt::launch_sample_part(dg, s->d_states, s->threads, bs, neg, (int)bern, (int)filter, calls,
-                                           parts, t->P.ent_total, wp, st));
+                                           parts, t->P.ent_total, w, st));
     } else {
         PT_TIMED(0, pt::launch_sample_csr(dg, s->d_states, s->threads, bs, neg, (int)bern, (int)filter, calls, w, st));
         PT_TIMED(1, pt::launch_scan_counts(w, t->P.ent_total, calls, s->d_states, s->threads, bs, dpp, st));
@@ -354,7 +315,7 @@ static int enqueue_run(pt_trainer *t, pt_sampler *s, int64_t bs, int64_t neg, in
         for (int64_t c0 = 0; c0 < steps; c0 += chunk) {
             const int64_t calls = std::min(chunk, steps - c0);
             // (sets t->csr.rank_only, read by the steps and by pt_trainer_run_timed's re-timing)
-            int rc = enqueue_sample_chunk(t, s, t->csr, bs, neg, bern, filter, calls, sample_mode(t), st, tm);
+            int rc = enqueue_sample_chunk(t, s, t->csr, bs, neg, bern, filter, calls, t->path_override, st, tm);
             if (rc) return rc;
             for (int64_t j = 0; j < calls; ++j) {
                 const pt::CsrWork v = pt::csr_view(t->csr, j, bs, neg);
@@ -666,38 +627,6 @@ extern "C" int pt_trainer_run_timed(pt_trainer *t, pt_sampler *s, int64_t bs, in
         tot[std::get<0>(e)] += ms;
     }
     for (int k = 0; k < 4; ++k) ms4[k] = (float)(tot[k] / (double)steps);
-    if (t->csr.prof && t->last_path == PT_PATH_PART && t->prof_calls > 0) {   // split sampler phases of the last chunk
-        const int64_t calls = t->prof_calls, parts = t->prof_parts;
-        std::vector<uint64_t> pr((size_t)(8 * calls * parts));
-        PT_HIP(hipMemcpy(pr.data(), t->csr.prof, 8 * pr.size(), hipMemcpyDeviceToHost));
-        uint64_t t0 = ~0ull, tend = 0;
-        double ph[7] = {0}, mx[7] = {0};
-        int64_t n_last = 0;
-        double last5 = 0, last6 = 0;
-        for (int64_t i = 0; i < calls * parts; ++i) t0 = std::min(t0, pr[8 * i]);
-        for (int64_t i = 0; i < calls * parts; ++i) {
-            const uint64_t *q = &pr[8 * i];
-            for (int k = 1; k <= 4; ++k) {
-                ph[k] += (double)(q[k] - q[k - 1]);
-                mx[k] = std::max(mx[k], (double)(q[k] - t0));
-            }
-            mx[0] = std::max(mx[0], (double)(q[0] - t0));
-            if (q[7]) {
-                ++n_last;
-                last5 += (double)(q[5] - q[4]);
-                last6 += (double)(q[6] - q[5]);
-                tend = std::max(tend, q[6]);
-            }
-        }
-        const double n = (double)(calls * parts);
-        fprintf(stderr,
-                "part-prof calls %ld parts %ld: avg us positives %.2f slots %.2f reserve %.2f rank+ticket %.2f | "
-                "last exchange %.2f scan %.2f | latest start %.2f, phase ends (max from first start) %.2f %.2f %.2f "
-                "%.2f, kernel end %.2f\n",
-                (long)calls, (long)parts, ph[1] / n / 100, ph[2] / n / 100, ph[3] / n / 100, ph[4] / n / 100,
-                last5 / std::max<int64_t>(n_last, 1) / 100, last6 / std::max<int64_t>(n_last, 1) / 100, mx[0] / 100,
-                mx[1] / 100, mx[2] / 100, mx[3] / 100, mx[4] / 100, (double)(tend - t0) / 100);
-    }
     if (!use_csr(neg)) return PT_OK;
     // Counting-sort path: the per-step kernels are re-timed back to back (as a captured epoch runs
     // them), one event pair per loop instead of one per launch, on the last pre-sampled batch:

@@ -3,7 +3,6 @@
 // lays out its device workspace and trains it with the persistent multi-universe kernel (universes.hip).
 #include <algorithm>
 #include <atomic>
-#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -15,7 +14,6 @@
 #include <unordered_map>
 #include <vector>
 
-#include "tuning.h"
 #include "common.h"
 #include "graph.h"
 #include "ordered.h"
@@ -30,12 +28,12 @@
 namespace {
 struct ClassStreamPool {
     std::mutex mu;
-    std::map<std::pair<int, int>, std::vector<hipStream_t>> by_dev;   // (device, mode) -> streams
+    std::map<int, std::vector<hipStream_t>> by_dev;   // device -> streams
     // destroyed when the library is unloaded (process exit): the HIP runtime, loaded before this library, is
     // finalized after it, so the queues are released while it still runs
     ~ClassStreamPool() {
         for (auto &kv : by_dev) {
-            if (hipSetDevice(kv.first.first) != hipSuccess) continue;
+            if (hipSetDevice(kv.first) != hipSuccess) continue;
             for (hipStream_t q : kv.second) (void)hipStreamDestroy(q);
         }
     }
@@ -44,39 +42,23 @@ ClassStreamPool &class_stream_pool() {
     static ClassStreamPool p;
     return p;
 }
-// mode 1: full-CU-mask streams (dedicated hardware queues; the product's choice); tuning builds also take
-// PT_UNI_STREAMS = 0 (round 4: per-set plain side streams, class 0 on the caller's stream), 2 (highest-priority
-// streams: their own queue pool), 3 (plain library streams)
-int class_stream_mode() {
-    static const int m = [] {
-        const char *v = pt_tuning_env("PT_UNI_STREAMS");
-        return v ? atoi(v) : 1;
-    }();
-    return m;
-}
-hipError_t class_streams(int device, int mode, size_t n, std::vector<hipStream_t> *out) {
+// n full-CU-mask streams of `device` (dedicated hardware queues), created on first use
+hipError_t class_streams(int device, size_t n, std::vector<hipStream_t> *out) {
     ClassStreamPool &P = class_stream_pool();
     std::lock_guard<std::mutex> lk(P.mu);
-    auto &v = P.by_dev[{device, mode}];
-    while (v.size() < n) {
-        hipStream_t q = nullptr;
-        hipError_t e = hipSuccess;
-        if (mode == 1) {
-            int cus = 0;
-            e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-            if (e != hipSuccess) return e;
-            std::vector<uint32_t> mask((size_t)(cus + 31) / 32, 0u);
-            for (int c = 0; c < cus; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
-            e = hipExtStreamCreateWithCUMask(&q, (uint32_t)mask.size(), mask.data());
-        } else if (mode == 2) {
-            int lo = 0, hi = 0;
-            e = hipDeviceGetStreamPriorityRange(&lo, &hi);
-            if (e == hipSuccess) e = hipStreamCreateWithPriority(&q, hipStreamNonBlocking, hi);
-        } else {
-            e = hipStreamCreateWithFlags(&q, hipStreamNonBlocking);
-        }
+    auto &v = P.by_dev[device];
+    if (v.size() < n) {
+        int cus = 0;
+        hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
         if (e != hipSuccess) return e;
-        v.push_back(q);
+        std::vector<uint32_t> mask((size_t)(cus + 31) / 32, 0u);
+        for (int c = 0; c < cus; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
+        while (v.size() < n) {
+            hipStream_t q = nullptr;
+            e = hipExtStreamCreateWithCUMask(&q, (uint32_t)mask.size(), mask.data());
+            if (e != hipSuccess) return e;
+            v.push_back(q);
+        }
     }
     out->assign(v.begin(), v.begin() + (std::ptrdiff_t)n);
     return hipSuccess;
@@ -108,7 +90,6 @@ struct pt_universe_set {
         int64_t share = 1;   // workgroups (= CUs) of its launch
     };
     std::vector<Group> groups;            // runs of d_us with one shape class (one kernel launch each)
-    std::vector<hipStream_t> streams;     // PT_UNI_STREAMS=0 only: per-set side streams (else the process pool's)
     std::vector<hipEvent_t> events;
     std::vector<hipEvent_t> t_start, t_stop;   // per group launch: timing events of the last train call
     bool timed = false;                        // the last train call recorded them
@@ -118,7 +99,7 @@ struct pt_universe_set {
     std::vector<int64_t> host_of_job;     // job index -> index in host / d_us
     std::vector<uint64_t> seeds0;         // [host][64]: the jobs' LCG states at creation (pt_universe_set_reset)
     void *graph_arena = nullptr;          // the universes' device graphs (one allocation, one copy)
-    uint64_t *prof = nullptr;             // PT_UNI_PROF=1: [n][64] cycle counters + shape (+ stamps) (device)
+    uint64_t *prof = nullptr;             // PT_UNI_PROF=1: [n][64] cycle counters + shape (device)
     // reference-order (deterministic) mode (pt_universe_set_deterministic): ordered.hip's universe kernel
     bool ordered = false;
     void *ord_arena = nullptr;            // per universe [4][seq][dim] gradient rows
@@ -127,7 +108,6 @@ struct pt_universe_set {
         for (auto e : events) (void)hipEventDestroy(e);
         for (auto e : t_start) (void)hipEventDestroy(e);
         for (auto e : t_stop) (void)hipEventDestroy(e);
-        for (auto q : streams) (void)hipStreamDestroy(q);
         if (arena) (void)hipFree(arena);
         if (prof) (void)hipFree(prof);
         if (ord_arena) (void)hipFree(ord_arena);
@@ -236,8 +216,6 @@ std::vector<int> choose_classes(const pt_universe_job *jobs, int64_t n, int32_t 
         if (launches.size() > 4) break;
         hot = h2;
     }
-    if (const char *v = pt_tuning_env("PT_UNI_HOT"))   // tuning: 0 = class kernels only
-        if (atoi(v) == 0) hot.clear();
     for (int64_t i = 0; i < n; ++i)
         if (hot.count(shape_v[i])) cls_v[i] = pt::kUniHotBase + shape_v[i];
     return cls_v;
@@ -361,41 +339,33 @@ struct Maxima {
 // then, each if it still fits, the relation gradient rows (the contended rows of the scatter), the
 // entity contribution lists (replace the entity float atomics), the touched flags, and as many
 // presampled batches as fit
-// tuning overrides (benchmarks): PT_UNI_RELGRAD / CONTRIB / LDSFLAGS / PRESAMPLE = 0 disable the
-// LDS placements, PT_UNI_FENCE=1 forces agent-scope fences
 int plan_lds(pt::UniverseLaunch &C, const Maxima &M, int64_t lds_budget, int32_t model, int64_t neg) {
     C.list_cap = std::max<int64_t>(M.bs * (4 + neg), 1);
     auto a4 = [](int64_t v) { return 4 * ((v + 3) & ~int64_t(3)); };
     const int64_t list_b = a4(C.list_cap);
     const int64_t relg_b = 4 * M.relg * (model == 1 ? 2 : 1);
     int64_t used = list_b;
-    auto env_on = [](const char *name) {
-        const char *v = pt_tuning_env(name);
-        return !v || atoi(v) != 0;
-    };
     PT_CHECK(used <= lds_budget, PT_EINVAL, "universe batch too large for the LDS work list");
     const int64_t per_batch = 12 * M.seq;
     // entity rows as contribution lists (heads for entities and relations, next per slot)
     const int64_t heads_b = a4(M.ent + 2 * M.rel) + a4(M.bs * (4 + neg));
-    C.contrib = used + heads_b <= lds_budget && env_on("PT_UNI_CONTRIB");
+    C.contrib = used + heads_b <= lds_budget;
     used += C.contrib ? heads_b : 0;
     // relation rows: LDS gradient rows (hot rows, few) if they fit, else contribution lists
-    C.lds_relgrad = used + relg_b <= lds_budget && env_on("PT_UNI_RELGRAD");
+    C.lds_relgrad = used + relg_b <= lds_budget;
     C.rel_list = C.contrib && !C.lds_relgrad;
     used += C.lds_relgrad ? relg_b : 0;
     // touched flags of the rows that are not lists
     const int64_t nfl = (C.contrib ? 0 : M.ent) + (C.rel_list ? 0 : 2 * M.rel);
     const int64_t flags_b = a4(nfl);
-    C.lds_flags = nfl > 0 && used + flags_b <= lds_budget && env_on("PT_UNI_LDSFLAGS");
+    C.lds_flags = nfl > 0 && used + flags_b <= lds_budget;
     used += C.lds_flags ? flags_b : 0;
-    C.pchunk = env_on("PT_UNI_PRESAMPLE") && per_batch > 0 ? std::min<int64_t>(M.nb, (lds_budget - used) / per_batch)
-                                                            : 0;
+    C.pchunk = per_batch > 0 ? std::min<int64_t>(M.nb, (lds_budget - used) / per_batch) : 0;
     if (C.pchunk < 0) C.pchunk = 0;
     used += C.pchunk * per_batch;
     C.lds_bytes = used;
     // agent-scope fences only while some gradient row is a global float atomic (or a flag global)
     C.agent_fence = !(C.contrib && (C.rel_list || (C.lds_relgrad && C.lds_flags)));
-    if (const char *v = pt_tuning_env("PT_UNI_FENCE")) C.agent_fence = C.agent_fence || atoi(v) != 0;
     C.threads = 512;
     return PT_OK;
 }
@@ -549,18 +519,8 @@ extern "C" int pt_universe_set_train(pt_universe_set *set, float *d_losses, void
     // onto the process's class streams (each on a hardware queue of its own, class_streams) and joined back, so
     // the launches overlap whatever streams the caller's process already holds
     const size_t ng = set->groups.size();
-    const int smode = class_stream_mode();
-    std::vector<hipStream_t> qs(ng);
-    if (smode == 0) {   // round 4's scheme (tuning A/B): class 0 on `st`, the others on per-set side streams
-        while (set->streams.size() + 1 < ng) {
-            hipStream_t q;
-            PT_HIP(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
-            set->streams.push_back(q);
-        }
-        for (size_t k = 0; k < ng; ++k) qs[k] = k == 0 ? st : set->streams[k - 1];
-    } else {
-        PT_HIP(class_streams(set->device, smode, ng, &qs));
-    }
+    std::vector<hipStream_t> qs;
+    PT_HIP(class_streams(set->device, ng, &qs));
     while (set->events.size() < ng + 1) {
         hipEvent_t ev;
         PT_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -574,28 +534,19 @@ extern "C" int pt_universe_set_train(pt_universe_set *set, float *d_losses, void
         set->t_stop.push_back(b);
     }
     PT_HIP(hipEventRecord(set->events[0], st));
-    for (size_t k = 0; k < ng; ++k)
-        if (qs[k] != st) PT_HIP(hipStreamWaitEvent(qs[k], set->events[0], 0));
+    for (size_t k = 0; k < ng; ++k) PT_HIP(hipStreamWaitEvent(qs[k], set->events[0], 0));
     for (size_t k = 0; k < ng; ++k) {
         const auto &gr = set->groups[k];
         const int64_t share = gr.share;
         hipStream_t q = qs[k];
         PT_HIP(hipEventRecord(set->t_start[k], q));
-        // PT_UNI_GRID=1 (tuning): one workgroup per universe in every launch, the hardware dispatcher
-        // interleaving the class launches as CUs free up, instead of a CU share per launch
-        static const bool per_universe = [] {
-            const char *v = pt_tuning_env("PT_UNI_GRID");
-            return v && atoi(v) != 0;
-        }();
-        const hipError_t e = pt::launch_universes(set->d_us + gr.off, gr.n, set->d_counter + k, gr.shape,
-                                                  per_universe ? gr.n : share,
+        const hipError_t e = pt::launch_universes(set->d_us + gr.off, gr.n, set->d_counter + k, gr.shape, share,
                                                   set->model, set->p_norm, set->norm_flag, set->opt, set->neg,
                                                   (int)set->bern, (int)set->filter, set->cfg, q);
         if (e != hipSuccess) return pt::fail(PT_EHIP, std::string("launch_universes: ") + hipGetErrorString(e));
         PT_HIP(hipEventRecord(set->t_stop[k], q));
     }
     for (size_t k = 0; k < ng; ++k) {
-        if (qs[k] == st) continue;
         PT_HIP(hipEventRecord(set->events[k + 1], qs[k]));
         PT_HIP(hipStreamWaitEvent(st, set->events[k + 1], 0));
     }
@@ -666,8 +617,8 @@ extern "C" int pt_universe_set_profiling(pt_universe_set *set, int32_t on) {
 
 // diagnostics: per universe (set order) 64 words: cycles in presampling / phase A / phase B, steps, batch size,
 // dim, entities, start / duration (100 MHz wall clock) of the last train call with profiling on; words 60-62
-// (the removed team universes' width, barrier cycles and phase-B rows) stay in the layout and stay zero; the other
-// words 8-63 phase stamps of one step (tuning build)
+// (the removed team universes' width, barrier cycles and phase-B rows) and words 8-59 (the removed measurement
+// build's phase stamps of one step) stay in the layout, reserved and zero; word 63: where the universe ran
 extern "C" int pt_universe_set_profile(pt_universe_set *set, uint64_t *out) {
     PT_CHECK(set && out, PT_EINVAL, "null argument");
     PT_CHECK(set->prof, PT_ESTATE, "profiling not enabled (pt_universe_set_profiling)");

@@ -19,12 +19,8 @@ Shape pick_universe_shape(int64_t D, bool wide) {
 int universe_shape_id(int64_t D, int model) {
     if (D <= 0) return -1;
     // TransE (few live rows per step) takes the wide shapes: twice the lane groups, half the rounds of a
-    // step's positives (PT_UNI_NARROW=1: the narrow ones)
-    static const bool narrow = [] {
-        const char *v = pt_tuning_env("PT_UNI_NARROW");
-        return v && atoi(v) != 0;
-    }();
-    const Shape s = pick_universe_shape(D, model == 0 && !narrow);
+    // step's positives
+    const Shape s = pick_universe_shape(D, model == 0);
     // (a shape its class kernel does not compile would leave the universe untrained: unsupported instead)
 #define PT_USUP(ID_, G_, V_, K_) \
     if (s.G == G_ && s.VEC == V_ && s.KCH == K_) return dev::shape_reachable(model, G_, V_, K_) ? ID_ : -1;

@@ -12,10 +12,8 @@ One process, device events, 20 warm-up steps, then the median of 5 runs of 100 s
     logsigmoid, softmax, backward, torch.optim.Adam on the dense tables - what a user would run without the kernels.
 The per-kernel figures repeat ONE device batch, so every step touches the same 128,000 corrupted rows and the same
 flagged rows: a friendlier cache state than training's fresh batches. The whole-step figures use fresh batches.
---lib PATH loads another build of the library (the measurement build, `make TUNING=1`, whose PT_ADV_STAGE=1 selects
-the LDS-staged pass 2 of k_step_adv and whose PT_ADV_NCH=1|2|4 sets the chunk depth of the shapes above dim 512) and
-records the variant under "pass2" / "k_step_adv_chunk_depth". k_step_adv is also reported against its float-atomic
-floor (the batch's corrupted rows at 1.3 TB/s), k_apply_adam against its six-pass HBM floor at 6.29 TB/s.
+--lib PATH loads another build of the library, for A/B runs of two builds. k_step_adv is also reported against its
+float-atomic floor (the batch's corrupted rows at 1.3 TB/s), k_apply_adam against its six-pass HBM floor at 6.29 TB/s.
 Prints one JSON line; --out also writes it to a file. Needs a GPU: there is no CPU path.
 """
 import argparse
@@ -43,7 +41,7 @@ def main():
     ap.add_argument("--dim", type=int, default=512)
     ap.add_argument("--data-dir", default=os.path.join(tempfile.gettempdir(), "putranse_bench_adv_%d" % os.getuid()))
     ap.add_argument("--out", default=None)
-    ap.add_argument("--lib", default=None, help="another build of libputranse_hip.so (measurement build)")
+    ap.add_argument("--lib", default=None, help="another build of libputranse_hip.so (A/B runs)")
     ap.add_argument("--skip-torch", action="store_true", help="leave out the torch-op step (A/B runs of the kernels)")
     args = ap.parse_args()
 
@@ -53,7 +51,6 @@ def main():
 
     import synth_kg
     from openke import _native
-    staged = bool(args.lib) and os.environ.get("PT_ADV_STAGE", "0") not in ("", "0")
     if args.lib:
         _native.use_alternative_library(args.lib)
     from openke.config import Trainer
@@ -170,7 +167,6 @@ def main():
         "k_step_adv_atomic_floor_bytes": atomic_bytes,
         "k_step_adv_atomic_floor_us_at_1.3TBps": atomic_bytes / atomic_rate * 1e6,
         "k_step_adv_fraction_of_atomic_floor": (atomic_bytes / atomic_rate * 1e6) / med(k_step),
-        "k_step_adv_chunk_depth": (os.environ.get("PT_ADV_NCH") if args.lib else None) or "default",
         "k_apply_adam_us": med(k_adam), "k_apply_adam_us_runs": k_adam,
         "k_apply_adam_floor_bytes": floor_bytes,
         "k_apply_adam_floor_us_at_6.29TBps": floor_bytes / hbm * 1e6,
@@ -178,7 +174,6 @@ def main():
         "native_step_us": med(whole), "native_step_us_runs": whole,
         "torch_step_us": med(torch_us) if torch_us else None, "torch_step_us_runs": torch_us,
         "native_over_torch_speedup": med(torch_us) / med(whole) if torch_us else None,
-        "pass2": "pass-1 rows staged in LDS" if staged else "re-reads rows (L2 / Infinity Cache)",
         "kernel_figures_note": "one repeated device batch (same rows every step); whole-step figures use fresh batches",
         "last_loss_native": native_loss, "last_loss_torch": float(last[0]) if torch_us else None,
     }

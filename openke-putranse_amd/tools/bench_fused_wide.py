@@ -5,9 +5,8 @@ plain MarginLoss, SGD, p 1, norm_flag on).
 neg selects k_step_csr's lane groups per positive (S 1 below 12 negatives, S 2 below 24, S 4 from there). Per
 (dim, neg): epochs of --steps steps are replayed until two consecutive ones agree within 1 % (clocks and caches
 settle over the first seconds: the early epochs run up to a fifth slower), then the median of --runs epochs is
-reported with every run, in microseconds per step, one JSON line each. --lib PATH loads the measurement build
-(`make TUNING=1`), whose PT_CSR_NCH=1|2 sets k_step_csr's chunk depth at these dims; the value is recorded.
-Needs a GPU: there is no CPU path.
+reported with every run, in microseconds per step, one JSON line each. --lib PATH loads another build of the library,
+for A/B runs of two builds. Needs a GPU: there is no CPU path.
 """
 import argparse
 import json
@@ -25,7 +24,7 @@ WN18RR = (40943, 11, 86835, 3034, 3134)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--lib", default=None, help="another build of libputranse_hip.so (measurement build)")
+    ap.add_argument("--lib", default=None, help="another build of libputranse_hip.so (A/B runs)")
     ap.add_argument("--dims", default="768,1024")
     ap.add_argument("--negs", default="8,12,25")
     ap.add_argument("--batch", type=int, default=2000)
@@ -87,7 +86,6 @@ def main():
             us = [epoch() for _ in range(args.runs)]
             lines.append(json.dumps({
                 "tool": "bench_fused_wide", "dim": D, "neg": neg, "batch": bs, "steps": args.steps,
-                "csr_chunk_depth": (os.environ.get("PT_CSR_NCH") if args.lib else None) or "default",
                 "warmup_epochs": warm, "fused_step_us": statistics.median(us), "fused_step_us_runs": us,
                 "last_loss": float(tr.last_step_losses[-1])}))
             print(lines[-1], flush=True)

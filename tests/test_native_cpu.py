@@ -398,3 +398,18 @@ def test_removed_step_apply_shim_without_trainer():
         assert L.pt_trainer_set_sample_split(None, h) == 1
     assert L.pt_trainer_step_apply(None) == 0
     assert L.pt_trainer_slot_scale(None) == 0
+
+
+def test_library_reads_no_environment():
+    """The library has one build and reads no environment variable: no source under csrc/ or include/ names getenv,
+    and the measurement build's switch header (csrc/tuning.h) is gone."""
+    csrc = os.path.join(REPO, "openke-putranse_amd", "csrc")
+    assert not os.path.exists(os.path.join(csrc, "tuning.h"))
+    scanned = 0
+    for top in (csrc, os.path.join(REPO, "include")):
+        for root, _, files in os.walk(top):
+            for name in files:
+                with open(os.path.join(root, name), errors="replace") as f:
+                    assert "getenv" not in f.read(), os.path.join(root, name)
+                scanned += 1
+    assert scanned > 30, scanned
