@@ -81,11 +81,18 @@ int pt_sampler_sample_ex(pt_sampler *s, int64_t bs, int64_t neg, int64_t neg_rel
  * SGD, Adagrad, Adam) and pt_score / pt_score_queries / pt_score_rows. In-kernel sampling, captured runs
  * (pt_trainer_run, pt_trainer_run_timed), the reference-order mode, any other loss and every universe entry point
  * (pt_universes_train*, pt_universe_set_create, pt_universe_dim_supported, pt_lp_min_scores) refuse it. */
-enum { PT_TRANSE = 0, PT_TRANSH = 1, PT_TRANSD = 2 };
+/* PT_ROTATE (RotatE.py): one model through pt_trainer_step on external batches (SigmoidLoss or MarginLoss, with or
+ * without the self-adversarial weights, always with the model's margin: pt_loss_desc.score_margin_flag = 1; SGD,
+ * Adagrad, Adam) and pt_score / pt_score_queries / pt_score_rows, which return the distance d (the caller subtracts
+ * the margin). pt_model_desc.dim is the relation row's: ent is [ent_total][2 * dim] (re | im), rel [rel_total][dim]
+ * phases, the Adagrad / Adam state shaped like them. A sampler passed to pt_trainer_step, pt_trainer_run,
+ * pt_trainer_run_timed, the reference-order mode and every universe entry point refuse it (PT_ENOTSUP). neg_ent is
+ * limited as for the weighted TransE step at the same dim. */
+enum { PT_TRANSE = 0, PT_TRANSH = 1, PT_TRANSD = 2, PT_ROTATE = 3 };
 enum { PT_SGD = 0, PT_ADAGRAD = 1, PT_ADAM = 2 };
 
 typedef struct {
-    int32_t model;        /* PT_TRANSE | PT_TRANSH | PT_TRANSD */
+    int32_t model;        /* PT_TRANSE | PT_TRANSH | PT_TRANSD | PT_ROTATE */
     int32_t p_norm;       /* 1 or 2  (TransE.py:46-60) */
     int32_t norm_flag;    /* F.normalize of h, r, t before scoring */
     int32_t opt;          /* PT_SGD | PT_ADAGRAD (Trainer.py:62-88; eps 1e-10, lr_decay 0) | PT_ADAM (state:
@@ -98,6 +105,9 @@ typedef struct {
     /* PT_TRANSD only (NULL otherwise): ent_transfer [ent_total][dim], rel_transfer [rel_total][dim] and their
      * Adagrad state_sum. Appended: a caller that zero-initialises the struct and fills the fields above is unchanged. */
     float *ent_transfer, *rel_transfer, *ent_transfer_acc, *rel_transfer_acc;
+    /* PT_ROTATE only (appended, ignored otherwise): the phase divisor q = float32(rel_embedding_range / pi); the phase
+     * of a relation element is r / q. Finite and > 0, else PT_EINVAL. */
+    float phase_div;
 } pt_model_desc;
 
 /* Workspace for minibatch-synchronous steps on one model (gradient rows, touched-row flags). */
@@ -146,8 +156,9 @@ int pt_trainer_get_deterministic(const pt_trainer *t);
  * positive's negatives, softmax(-temperature * n) for the margin loss and softmax(temperature * n) for the sigmoid
  * loss, constants of the backward pass (else 1 / neg). score_margin_flag != 0: the model carries its own margin
  * (TransE.py:62-67) and the score handed to the loss is score_margin - d instead of the distance d.
- * Anything but the default trains TransE only, on external batches only (PT_ENOTSUP from pt_trainer_step with
- * batch_h == NULL, pt_trainer_run, pt_trainer_run_timed, the reference-order mode and TransH). */
+ * Anything but the default trains TransE and RotatE only, on external batches only (PT_ENOTSUP from pt_trainer_step
+ * with batch_h == NULL, pt_trainer_run, pt_trainer_run_timed, the reference-order mode and TransH). PT_ROTATE needs
+ * score_margin_flag != 0 (RotatE.py:86: its score is always margin - distance). */
 enum { PT_LOSS_MARGIN = 0, PT_LOSS_SIGMOID = 1 };
 typedef struct {
     int32_t kind;               /* PT_LOSS_MARGIN | PT_LOSS_SIGMOID */
@@ -175,8 +186,8 @@ int pt_trainer_set_adam(pt_trainer *t, const pt_adam_state *state);
 int64_t pt_trainer_adam_step(const pt_trainer *t);
 /* Measurement hook of the external-batch step (tools/bench_adv.py): `steps` steps on ONE device batch (layout of
  * pt_trainer_step), launched one by one with events around both launches of every step. ms2[0] = mean duration of
- * the step kernel (k_step / k_step_adv / k_step_transd), ms2[1] = of the apply kernel (k_apply / k_apply_adam; both
- * launches of it for PT_TRANSD). The steps train:
+ * the step kernel (k_step / k_step_adv / k_step_transd / k_step_rotate), ms2[1] = of the apply kernel (k_apply /
+ * k_apply_adam; both launches of it for PT_TRANSD). The steps train:
  * tables, optimizer state and the Adam step count advance, *d_loss accumulates. Synchronizes the stream. */
 int pt_trainer_steps_timed(pt_trainer *t, int64_t bs, int64_t neg, const int64_t *d_batch_h, const int64_t *d_batch_t,
                            const int64_t *d_batch_r, int64_t steps, float *d_loss, float *ms2, void *stream);
@@ -221,7 +232,8 @@ int pt_trainer_sample_csr(pt_trainer *t, pt_sampler *sampler, int64_t bs, int64_
 /* ------------------------------------------------------------------ scoring ------------------ */
 /* scores = ||h + r - t||_p as model.predict computes them (TransE.py:46-74, TransH.py:52-93, TransD.py:94-129):
  * mode 0 normal (all three arrays length n), 1 head_batch (d_h length n, t and r length 1),
- * 2 tail_batch (d_t length n, h and r length 1). */
+ * 2 tail_batch (d_t length n, h and r length 1). PT_ROTATE: the distance sum_j |h_j e^(i r_j / q) - t_j| of
+ * RotatE.py:45-76 (head_batch: its conjugate form); the model's predict subtracts its margin. */
 int pt_score(const pt_model_desc *m, int32_t mode, const int64_t *d_h, const int64_t *d_t, const int64_t *d_r,
              int64_t n, float *d_out, void *stream);
 
@@ -306,7 +318,9 @@ int pt_universe_set_launch_times(pt_universe_set *s, int64_t cap, float *out, in
 int pt_universe_dim_supported(int64_t dim, int32_t model);
 /* 1 when a single model of embedding dim `dim` is accepted by pt_trainer_create / pt_score* (pt_model_desc.dim):
  * PT_TRANSE / PT_TRANSH at dims 1..512 and at multiples of 4 from 516 to 1024 (float4 rows), PT_TRANSD at dims
- * 1..512; else 0 (those calls then fail with PT_ENOTSUP). No device call. */
+ * 1..512; else 0 (those calls then fail with PT_ENOTSUP). No device call. It answers for these three models, as it
+ * did before PT_ROTATE existed, and 0 for every other model id, 3 (PT_ROTATE) included: callers use 3 as an id no
+ * model has. PT_ROTATE's pt_model_desc.dim (its relation row's) follows PT_TRANSE's rule: ask with PT_TRANSE. */
 int pt_model_dim_supported(int64_t dim, int32_t model);
 /* reference-order (deterministic) mode of a set (see pt_trainer_set_deterministic): one workgroup per
  * universe runs its steps with the ordered per-row sums; its workspace is allocated on first use */

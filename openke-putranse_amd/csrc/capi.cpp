@@ -4,6 +4,7 @@
 // pt_universes_train, is universe_set.cpp; the reference's Base.so symbols are legacy.cpp.)
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <string>
 #include <thread>
 #include <vector>
@@ -33,8 +34,8 @@ extern "C" int pt_version(void) { return 1; }
 // ======================================================================== model descriptor =======
 int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
     PT_CHECK(m, PT_EINVAL, "null model descriptor");
-    PT_CHECK(m->model == PT_TRANSE || m->model == PT_TRANSH || m->model == PT_TRANSD, PT_EINVAL,
-             "model must be PT_TRANSE, PT_TRANSH or PT_TRANSD");
+    PT_CHECK(m->model == PT_TRANSE || m->model == PT_TRANSH || m->model == PT_TRANSD || m->model == PT_ROTATE,
+             PT_EINVAL, "model must be PT_TRANSE, PT_TRANSH, PT_TRANSD or PT_ROTATE");
     PT_CHECK(m->p_norm == 1 || m->p_norm == 2, PT_ENOTSUP, "p_norm must be 1 or 2");
     PT_CHECK(m->opt == PT_SGD || m->opt == PT_ADAGRAD || m->opt == PT_ADAM, PT_EINVAL,
              "opt must be PT_SGD, PT_ADAGRAD or PT_ADAM");
@@ -42,7 +43,9 @@ int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
              "embedding dim " + std::to_string(m->dim) + " not supported: TransD takes dims 1..512");
     PT_CHECK(pt::model_dim_supported(m->dim, m->model), PT_ENOTSUP,
              "embedding dim " + std::to_string(m->dim) +
-                 " not supported: TransE and TransH take dims 1..512 and multiples of 4 from 516 to 1024");
+                 " not supported: TransE, TransH and RotatE take dims 1..512 and multiples of 4 from 516 to 1024");
+    PT_CHECK(m->model != PT_ROTATE || (std::isfinite(m->phase_div) && m->phase_div > 0.f), PT_EINVAL,
+             "PT_ROTATE needs a finite phase divisor > 0 (pt_model_desc.phase_div = rel_embedding_range / pi)");
     PT_CHECK(m->ent && m->rel && m->ent_total > 0 && m->rel_total > 0, PT_EINVAL, "missing tables");
     PT_CHECK(m->model != PT_TRANSH || m->normv, PT_EINVAL, "TransH needs norm_vector");
     PT_CHECK(m->model != PT_TRANSD || (m->ent_transfer && m->rel_transfer), PT_EINVAL,
@@ -61,6 +64,7 @@ int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
     P.dim = m->dim;
     P.ent = m->ent; P.rel = m->rel; P.normv = m->normv;
     P.ent_acc = m->ent_acc; P.rel_acc = m->rel_acc; P.norm_acc = m->norm_acc;
+    if (m->model == PT_ROTATE) P.phase_div = m->phase_div;
     if (m->model == PT_TRANSD) {
         P.ent_t = m->ent_transfer; P.rel_t = m->rel_transfer;
         P.ent_t_acc = m->ent_transfer_acc; P.rel_t_acc = m->rel_transfer_acc;
@@ -68,8 +72,9 @@ int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
     return PT_OK;
 }
 
+// (answers for the three translational models, as it always has: PT_ROTATE's dims are PT_TRANSE's, putranse.h)
 extern "C" int pt_model_dim_supported(int64_t dim, int32_t model) {
-    return pt::model_dim_supported(dim, model) ? 1 : 0;
+    return model != PT_ROTATE && pt::model_dim_supported(dim, model) ? 1 : 0;
 }
 
 // ======================================================================== graphs =================
@@ -336,6 +341,7 @@ extern "C" int pt_lp_min_scores(const pt_lp_universe *us, int64_t n_universes, i
                                 int32_t norm_flag, const pt_lp_pair *pairs, int64_t n_pairs,
                                 int64_t global_ent_total, float *d_key_rows, float *d_key_tuple, void *stream) {
     PT_CHECK(model != PT_TRANSD, PT_ENOTSUP, "pt_lp_min_scores: PuTransD universes are not built yet (PT_TRANSD)");
+    PT_CHECK(model != PT_ROTATE, PT_ENOTSUP, "pt_lp_min_scores: PT_ROTATE trains and ranks one model, not universes");
     PT_CHECK((us && pairs && d_key_rows) || n_pairs == 0, PT_EINVAL, "pt_lp_min_scores: null argument");
     if (n_pairs == 0) return PT_OK;
     hipStream_t st = (hipStream_t)stream;

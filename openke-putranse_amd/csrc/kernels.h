@@ -22,6 +22,8 @@ struct StepParams {
     // places in the argument blocks of the TransE / TransH kernels)
     float *ent_t = nullptr, *rel_t = nullptr;
     float *ent_t_acc = nullptr, *rel_t_acc = nullptr;
+    // RotatE (model 3): an entity row holds 2 * dim floats (re | im), a relation row dim phases; phase = r / phase_div
+    float phase_div = 0.f;
 };
 
 struct StepWorkspace {
@@ -99,7 +101,7 @@ constexpr Shape pick_shape(int64_t D, bool vec4 = true) {
 }
 
 // instantiated (G, VEC, KCH) row shapes: float4 rows up to dim 1,024 (KCH 3 and 4: dims 516..1,024, TransE and TransH
-// single models only; model_dim_supported is the rule), one-float rows up to dim 512
+// and RotatE single models only; model_dim_supported is the rule), one-float rows up to dim 512
 #define PT_SHAPES(X)                                                                                  \
     X(2, 4, 1) X(4, 4, 1) X(8, 4, 1) X(16, 4, 1) X(32, 4, 1) X(64, 4, 1) X(64, 4, 2) X(64, 4, 3)     \
     X(64, 4, 4)                                                                                       \
@@ -131,8 +133,9 @@ constexpr bool for_value(int v, F &&f) {
 }
 
 // ---- kernels.hip: the dim rule and the score kernels
-// The one dim rule of the single-model path (pt_model_dim_supported): dims 1..512 for every model (both row layouts
-// exist), dims 516..1,024 in multiples of 4 (float4 rows only) for TransE (0) and TransH (1); nothing else
+// The one dim rule of the single-model path (pt_model_dim_supported answers it for models 0-2): dims 1..512 for every model (both row layouts
+// exist), dims 516..1,024 in multiples of 4 (float4 rows only) for TransE (0), TransH (1) and RotatE (3); nothing
+// else. RotatE's dim is its relation row's: an entity row is two such rows, re | im
 bool model_dim_supported(int64_t dim, int model);
 // dims at which both row layouts exist (1..512): what the one-float kernels (k_step_sampled, k_lp_scan_t's tile) take
 bool narrow_dim_supported(int64_t dim);
@@ -234,6 +237,27 @@ inline void transd_transfer_pass(const StepParams &P, const StepWorkspace &W, St
     W2->gent = W.gentt; W2->grel = W.grelt;
     W2->fent = W.fentt; W2->frel = W.frelt;
     W2->lpart = nullptr;
+}
+
+// RotatE (rotate.hip): the external-batch step under every loss LossParams expresses (the score handed to the loss is
+// gamma - d, always), and the distances d behind pt_score*; launch_score / launch_score_queries route model 3 to the
+// latter two. The gradient rows, flags and optimizer state of the entity table are [2 * ent_total][dim] half rows:
+// the optimizer pass runs once, on rotate_half_rows' view
+int64_t step_rotate_max_neg(int64_t dim);
+hipError_t launch_step_rotate(const StepParams &P, const LossParams &L, const int64_t *bh, const int64_t *bt,
+                              const int64_t *br, const StepWorkspace &W, hipStream_t st);
+hipError_t launch_score_rotate(const StepParams &P, int mode, const int64_t *h, const int64_t *t, const int64_t *r,
+                               int64_t n, float *out, hipStream_t st);
+hipError_t launch_score_queries_rotate(const StepParams &P, int side, const int64_t *qh, const int64_t *qt,
+                                       const int64_t *qr, int64_t nq, int64_t E, float *out, hipStream_t st,
+                                       int global_order);
+// a RotatE model's tables as the optimizer passes see them: the entity table as 2 * ent_total rows of dim floats
+// (every float of it is a parameter of its own: no Jacobian), the phases as they are
+inline StepParams rotate_half_rows(const StepParams &P) {
+    StepParams Q = P;
+    Q.ent_total = 2 * P.ent_total;
+    Q.norm_flag = 0;
+    return Q;
 }
 
 hipError_t launch_torch_init(const pt_torch_init_job *d_jobs, int64_t n, hipStream_t st);

@@ -56,7 +56,9 @@ struct pt_trainer {
     bool adam_set = false;
     int64_t adam_step = 0;   // steps done
     // anything the in-kernel-sampled, captured and reference-order paths do not compute
-    bool extended() const { return !loss.plain() || P.opt == PT_ADAM || P.model == PT_TRANSD; }
+    bool extended() const {
+        return !loss.plain() || P.opt == PT_ADAM || P.model == PT_TRANSD || P.model == PT_ROTATE;
+    }
     void drop_graphs() {
         for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
         graphs.clear();
@@ -109,7 +111,8 @@ extern "C" int pt_trainer_create(const pt_model_desc *m, pt_trainer **out) {
     int rc = pt::desc_to_params(m, t->P);
     if (rc) return rc;
     PT_HIP(hipGetDevice(&t->device));
-    const int64_t E = t->P.ent_total, R = t->P.rel_total, D = t->P.dim;
+    // (RotatE: gradient rows and flags of the entity table are half rows, 2 * ent_total of them)
+    const int64_t E = (m->model == PT_ROTATE ? 2 : 1) * t->P.ent_total, R = t->P.rel_total, D = t->P.dim;
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t ge = al(4 * E * D), gr = al(4 * R * D), gn = m->model == PT_TRANSH ? al(4 * R * D) : 0;
     const size_t fe = al(4 * E), fr = al(4 * R), fn = m->model == PT_TRANSH ? al(4 * R) : 0;
@@ -348,7 +351,17 @@ static int enqueue_external(pt_trainer *t, int64_t bs, int64_t neg, const int64_
     float scale = P.inv_count, cst = P.margin;   // loss = scale * sum(lpart) + cst
     if (ev) PT_HIP(hipEventRecord(ev[0], st));
     const bool transd = P.model == PT_TRANSD;
-    if (transd) {
+    if (P.model == PT_ROTATE) {
+        PT_CHECK(t->loss.mflag, PT_ENOTSUP,
+                 "PT_ROTATE scores gamma - d: pt_trainer_set_loss with score_margin_flag = 1 and the model's margin "
+                 "must come before the first step");
+        PT_CHECK(neg <= pt::step_rotate_max_neg(P.dim), PT_ENOTSUP,
+                 "neg_ent " + std::to_string(neg) + " too large for the PT_ROTATE step's LDS score buffer (max " +
+                     std::to_string(pt::step_rotate_max_neg(P.dim)) + ")");
+        pt::loss_affine(t->loss, P, &scale, &cst);
+        PT_HIP(pt::launch_step_rotate(P, t->loss, bh, bt, br, t->W, st));
+        P = pt::rotate_half_rows(P);   // the optimizer passes see the entity table as half rows
+    } else if (transd) {
         PT_CHECK(t->loss.plain(), PT_ENOTSUP,
                  "SigmoidLoss, adversarial weights and a model margin train TransE only (TransD is not implemented)");
         PT_HIP(pt::launch_step_transd(P, bh, bt, br, t->W, st));
@@ -396,8 +409,8 @@ static int enqueue_external(pt_trainer *t, int64_t bs, int64_t neg, const int64_
 }
 
 static const char *kExtendedMsg =
-    "a non-default loss (pt_trainer_set_loss), PT_ADAM and PT_TRANSD train external batches only: in-kernel sampling, "
-    "captured runs and the reference-order mode are not implemented for them";
+    "a non-default loss (pt_trainer_set_loss), PT_ADAM, PT_TRANSD and PT_ROTATE train external batches only: in-kernel "
+    "sampling, captured runs and the reference-order mode are not implemented for them";
 
 // per-positive loss partials for batches of up to `bs` positives (grown on demand, never during a
 // capture: callers prepare before enqueueing)
@@ -500,6 +513,7 @@ extern "C" int pt_trainer_set_deterministic(pt_trainer *t, int32_t on) {
     PT_CHECK(t, PT_EINVAL, "null trainer");
     PT_CHECK(!on || pt::ordered_dim_supported(t->P.dim), PT_ENOTSUP, "reference-order mode: dim too large");
     PT_CHECK(!on || t->P.model != PT_TRANSD, PT_ENOTSUP, "reference-order mode is not implemented for TransD");
+    PT_CHECK(!on || t->P.model != PT_ROTATE, PT_ENOTSUP, "reference-order mode is not implemented for PT_ROTATE");
     t->ordered = on != 0;
     return PT_OK;
 }
@@ -515,7 +529,7 @@ extern "C" int pt_trainer_set_loss(pt_trainer *t, const pt_loss_desc *l) {
     L.temp = l->adv ? l->temperature : 0.f;
     L.mflag = l->score_margin_flag ? 1 : 0;
     L.gamma = l->score_margin_flag ? l->score_margin : 0.f;
-    PT_CHECK(L.plain() || t->P.model == PT_TRANSE, PT_ENOTSUP,
+    PT_CHECK(L.plain() || t->P.model == PT_TRANSE || t->P.model == PT_ROTATE, PT_ENOTSUP,
              "SigmoidLoss, adversarial weights and a model margin train TransE only (TransH is not implemented)");
     t->loss = L;
     return PT_OK;

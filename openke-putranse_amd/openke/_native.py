@@ -20,7 +20,7 @@ c_u64p = ctypes.POINTER(ctypes.c_uint64)
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_f32p = ctypes.POINTER(ctypes.c_float)
 
-PT_TRANSE, PT_TRANSH, PT_TRANSD = 0, 1, 2
+PT_TRANSE, PT_TRANSH, PT_TRANSD, PT_ROTATE = 0, 1, 2, 3
 PT_SGD, PT_ADAGRAD, PT_ADAM = 0, 1, 2
 PT_LOSS_MARGIN, PT_LOSS_SIGMOID = 0, 1
 PT_DETERMINISTIC = 1   # pt_universes_train_ex flag: reference-order (deterministic) mode
@@ -39,7 +39,9 @@ class ModelDesc(ctypes.Structure):
                 ("margin", c_f32), ("ent_total", c_i64), ("rel_total", c_i64), ("dim", c_i64), ("ent", c_vp),
                 ("rel", c_vp), ("normv", c_vp), ("ent_acc", c_vp), ("rel_acc", c_vp), ("norm_acc", c_vp),
                 # PT_TRANSD only (NULL otherwise)
-                ("ent_transfer", c_vp), ("rel_transfer", c_vp), ("ent_transfer_acc", c_vp), ("rel_transfer_acc", c_vp)]
+                ("ent_transfer", c_vp), ("rel_transfer", c_vp), ("ent_transfer_acc", c_vp), ("rel_transfer_acc", c_vp),
+                # PT_ROTATE only: the phase divisor rel_embedding_range / pi
+                ("phase_div", c_f32)]
 
 
 class LossDesc(ctypes.Structure):

@@ -10,7 +10,8 @@ end of the epoch (one host sync per epoch instead of one per step). Cross sampli
 corruption (neg_rel > 0) train batch by batch: GPU-sampled batch, then the external-batch step. So do
 TransE under SigmoidLoss, the self-adversarial weights (adv_temperature) or a model margin (k_step_adv),
 and Adam (k_apply_adam, dense) for either model, and every TransD step (k_step_transd: plain MarginLoss with SGD,
-Adagrad or Adam)."""
+Adagrad or Adam), and every RotatE step (k_step_rotate: SigmoidLoss or MarginLoss, with or without the adversarial
+weights, always on the model's margin; SGD, Adagrad or Adam)."""
 import ctypes
 import os
 
@@ -78,7 +79,7 @@ class Trainer(object):
         if not isinstance(loss, (MarginLoss, SigmoidLoss)):
             raise NotImplementedError("loss %s is outside the accelerated path (MarginLoss and SigmoidLoss are)"
                                       % type(loss).__name__)
-        if self._weighted(kge, loss) and kge.native_model != _native.PT_TRANSE:
+        if self._weighted(kge, loss) and kge.native_model not in (_native.PT_TRANSE, _native.PT_ROTATE):
             raise NotImplementedError("SigmoidLoss, adversarial temperature and a model margin are accelerated for "
                                       "TransE only")
         if ns.regul_rate != 0 or ns.l3_regul_rate != 0:
@@ -109,6 +110,8 @@ class Trainer(object):
             self.optimizer = NativeOptimizer(method, self.alpha, kge.tables())
         opt = self.optimizer
         weighted = self._weighted(kge, loss)
+        if self.deterministic and kge.native_model == _native.PT_ROTATE:
+            raise NotImplementedError("deterministic=True (reference-order mode) is not implemented for RotatE")
         if self.deterministic and (weighted or opt.method == _native.PT_ADAM):
             raise NotImplementedError("deterministic=True (reference-order mode) covers plain MarginLoss with SGD or "
                                       "Adagrad only")
@@ -149,7 +152,7 @@ class Trainer(object):
     def _external_only(self, kge, loss):
         """Whether every step goes through the external-batch step (k_step / k_step_adv + k_apply / k_apply_adam)."""
         return (self._weighted(kge, loss) or self.optimizer.method == _native.PT_ADAM
-                or kge.native_model == _native.PT_TRANSD)
+                or kge.native_model in (_native.PT_TRANSD, _native.PT_ROTATE))
 
     def _sync_step(self):
         if self.optimizer.method == _native.PT_ADAM:

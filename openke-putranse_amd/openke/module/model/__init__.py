@@ -4,5 +4,6 @@ from .Model import Model
 from .TransE import TransE
 from .TransH import TransH
 from .TransD import TransD
+from .RotatE import RotatE
 
-__all__ = ['Model', 'TransE', 'TransH', 'TransD']
+__all__ = ['Model', 'TransE', 'TransH', 'TransD', 'RotatE']
