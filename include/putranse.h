@@ -88,11 +88,18 @@ int pt_sampler_sample_ex(pt_sampler *s, int64_t bs, int64_t neg, int64_t neg_rel
  * phases, the Adagrad / Adam state shaped like them. A sampler passed to pt_trainer_step, pt_trainer_run,
  * pt_trainer_run_timed, the reference-order mode and every universe entry point refuse it (PT_ENOTSUP). neg_ent is
  * limited as for the weighted TransE step at the same dim. */
-enum { PT_TRANSE = 0, PT_TRANSH = 1, PT_TRANSD = 2, PT_ROTATE = 3 };
+/* PT_DISTMULT (DistMult.py): one model through pt_trainer_step on external batches and pt_score / pt_score_queries /
+ * pt_score_rows, which return -sum_j h_j r_j t_j (what predict returns: lower is better, as for every other model).
+ * Tables as PT_TRANSE's, nothing normalised; p_norm, norm_flag, normv and phase_div are not read. The score goes to
+ * the loss as it is: PT_LOSS_SIGMOID only (SoftplusLoss.py is the same function), with or without the adversarial
+ * weights, score_margin_flag = 0; PT_LOSS_MARGIN, a model margin, a sampler passed to pt_trainer_step, pt_trainer_run,
+ * pt_trainer_run_timed, the reference-order mode and every universe entry point refuse it (PT_ENOTSUP). The model's
+ * regularisers come through pt_trainer_set_regul. neg_ent is limited as for the weighted TransE step at the same dim. */
+enum { PT_TRANSE = 0, PT_TRANSH = 1, PT_TRANSD = 2, PT_ROTATE = 3, PT_DISTMULT = 4 };
 enum { PT_SGD = 0, PT_ADAGRAD = 1, PT_ADAM = 2 };
 
 typedef struct {
-    int32_t model;        /* PT_TRANSE | PT_TRANSH | PT_TRANSD | PT_ROTATE */
+    int32_t model;        /* PT_TRANSE | PT_TRANSH | PT_TRANSD | PT_ROTATE | PT_DISTMULT */
     int32_t p_norm;       /* 1 or 2  (TransE.py:46-60) */
     int32_t norm_flag;    /* F.normalize of h, r, t before scoring */
     int32_t opt;          /* PT_SGD | PT_ADAGRAD (Trainer.py:62-88; eps 1e-10, lr_decay 0) | PT_ADAM (state:
@@ -183,11 +190,26 @@ typedef struct {
     float *ent_transfer_m, *rel_transfer_m, *ent_transfer_v, *rel_transfer_v;
 } pt_adam_state;
 int pt_trainer_set_adam(pt_trainer *t, const pt_adam_state *state);
+/* Regularisation of the external-batch step (NegativeSampling.py:28-31), PT_DISTMULT only; a plain host-side setter,
+ * read by the next step. regul_rate: DistMult.regularization, regul_rate * (mean h^2 + mean t^2 + mean r^2) / 3 over
+ * the rows of the batch as the data loader handed them over - batch_mode says how (0 normal: every slot's three rows;
+ * 1 head_batch / 2 tail_batch, as pt_score: the varying side per slot, the fixed side and the relation once per
+ * positive; pt_trainer_step still takes the expanded arrays). It is computed inside the step kernel and works with
+ * every optimizer. l3_regul_rate: DistMult.l3_regularization, l3 * (||ent||_3^3 + ||rel||_3^3) over the whole tables;
+ * dense, so it rides the PT_ADAM pass only: a step with l3_regul_rate != 0 under PT_SGD / PT_ADAGRAD returns
+ * PT_ENOTSUP. Both join the step's loss value. A nonzero rate on any other model: PT_ENOTSUP; a negative or
+ * non-finite rate, batch_mode outside 0..2: PT_EINVAL. */
+typedef struct {
+    float regul_rate, l3_regul_rate;
+    int32_t batch_mode;   /* 0 normal, 1 head_batch, 2 tail_batch */
+} pt_regul_desc;
+int pt_trainer_set_regul(pt_trainer *t, const pt_regul_desc *r);
 int64_t pt_trainer_adam_step(const pt_trainer *t);
 /* Measurement hook of the external-batch step (tools/bench_adv.py): `steps` steps on ONE device batch (layout of
  * pt_trainer_step), launched one by one with events around both launches of every step. ms2[0] = mean duration of
- * the step kernel (k_step / k_step_adv / k_step_transd / k_step_rotate), ms2[1] = of the apply kernel (k_apply /
- * k_apply_adam; both launches of it for PT_TRANSD). The steps train:
+ * the step kernel (k_step / k_step_adv / k_step_transd / k_step_rotate / k_step_distmult), ms2[1] = of the apply
+ * kernel (k_apply / k_apply_adam; both launches of it for PT_TRANSD; with l3_regul_rate its loss launch too). The
+ * steps train:
  * tables, optimizer state and the Adam step count advance, *d_loss accumulates. Synchronizes the stream. */
 int pt_trainer_steps_timed(pt_trainer *t, int64_t bs, int64_t neg, const int64_t *d_batch_h, const int64_t *d_batch_t,
                            const int64_t *d_batch_r, int64_t steps, float *d_loss, float *ms2, void *stream);
@@ -320,7 +342,8 @@ int pt_universe_dim_supported(int64_t dim, int32_t model);
  * PT_TRANSE / PT_TRANSH at dims 1..512 and at multiples of 4 from 516 to 1024 (float4 rows), PT_TRANSD at dims
  * 1..512; else 0 (those calls then fail with PT_ENOTSUP). No device call. It answers for these three models, as it
  * did before PT_ROTATE existed, and 0 for every other model id, 3 (PT_ROTATE) included: callers use 3 as an id no
- * model has. PT_ROTATE's pt_model_desc.dim (its relation row's) follows PT_TRANSE's rule: ask with PT_TRANSE. */
+ * model has. PT_ROTATE's pt_model_desc.dim (its relation row's) follows PT_TRANSE's rule: ask with PT_TRANSE. The
+ * same holds for 4 (PT_DISTMULT): 0 here, PT_TRANSE's rule in pt_trainer_create / pt_score*. */
 int pt_model_dim_supported(int64_t dim, int32_t model);
 /* reference-order (deterministic) mode of a set (see pt_trainer_set_deterministic): one workgroup per
  * universe runs its steps with the ordered per-row sums; its workspace is allocated on first use */

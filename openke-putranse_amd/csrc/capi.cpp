@@ -34,16 +34,17 @@ extern "C" int pt_version(void) { return 1; }
 // ======================================================================== model descriptor =======
 int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
     PT_CHECK(m, PT_EINVAL, "null model descriptor");
-    PT_CHECK(m->model == PT_TRANSE || m->model == PT_TRANSH || m->model == PT_TRANSD || m->model == PT_ROTATE,
-             PT_EINVAL, "model must be PT_TRANSE, PT_TRANSH, PT_TRANSD or PT_ROTATE");
-    PT_CHECK(m->p_norm == 1 || m->p_norm == 2, PT_ENOTSUP, "p_norm must be 1 or 2");
+    PT_CHECK(m->model == PT_TRANSE || m->model == PT_TRANSH || m->model == PT_TRANSD || m->model == PT_ROTATE ||
+                 m->model == PT_DISTMULT,
+             PT_EINVAL, "model must be PT_TRANSE, PT_TRANSH, PT_TRANSD, PT_ROTATE or PT_DISTMULT");
+    PT_CHECK(m->model == PT_DISTMULT || m->p_norm == 1 || m->p_norm == 2, PT_ENOTSUP, "p_norm must be 1 or 2");
     PT_CHECK(m->opt == PT_SGD || m->opt == PT_ADAGRAD || m->opt == PT_ADAM, PT_EINVAL,
              "opt must be PT_SGD, PT_ADAGRAD or PT_ADAM");
     PT_CHECK(m->model != PT_TRANSD || pt::model_dim_supported(m->dim, m->model), PT_ENOTSUP,
              "embedding dim " + std::to_string(m->dim) + " not supported: TransD takes dims 1..512");
     PT_CHECK(pt::model_dim_supported(m->dim, m->model), PT_ENOTSUP,
              "embedding dim " + std::to_string(m->dim) +
-                 " not supported: TransE, TransH and RotatE take dims 1..512 and multiples of 4 from 516 to 1024");
+                 " not supported: TransE, TransH, RotatE and DistMult take dims 1..512 and multiples of 4 from 516 to 1024");
     PT_CHECK(m->model != PT_ROTATE || (std::isfinite(m->phase_div) && m->phase_div > 0.f), PT_EINVAL,
              "PT_ROTATE needs a finite phase divisor > 0 (pt_model_desc.phase_div = rel_embedding_range / pi)");
     PT_CHECK(m->ent && m->rel && m->ent_total > 0 && m->rel_total > 0, PT_EINVAL, "missing tables");
@@ -65,6 +66,11 @@ int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
     P.ent = m->ent; P.rel = m->rel; P.normv = m->normv;
     P.ent_acc = m->ent_acc; P.rel_acc = m->rel_acc; P.norm_acc = m->norm_acc;
     if (m->model == PT_ROTATE) P.phase_div = m->phase_div;
+    if (m->model == PT_DISTMULT) {   // (p_norm, norm_flag and normv are not read: nothing of it is normalised)
+        P.p_norm = 1;
+        P.norm_flag = 0;
+        P.normv = nullptr;
+    }
     if (m->model == PT_TRANSD) {
         P.ent_t = m->ent_transfer; P.rel_t = m->rel_transfer;
         P.ent_t_acc = m->ent_transfer_acc; P.rel_t_acc = m->rel_transfer_acc;
@@ -74,7 +80,7 @@ int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
 
 // (answers for the three translational models, as it always has: PT_ROTATE's dims are PT_TRANSE's, putranse.h)
 extern "C" int pt_model_dim_supported(int64_t dim, int32_t model) {
-    return model != PT_ROTATE && pt::model_dim_supported(dim, model) ? 1 : 0;
+    return model != PT_ROTATE && model != PT_DISTMULT && pt::model_dim_supported(dim, model) ? 1 : 0;
 }
 
 // ======================================================================== graphs =================
@@ -342,6 +348,8 @@ extern "C" int pt_lp_min_scores(const pt_lp_universe *us, int64_t n_universes, i
                                 int64_t global_ent_total, float *d_key_rows, float *d_key_tuple, void *stream) {
     PT_CHECK(model != PT_TRANSD, PT_ENOTSUP, "pt_lp_min_scores: PuTransD universes are not built yet (PT_TRANSD)");
     PT_CHECK(model != PT_ROTATE, PT_ENOTSUP, "pt_lp_min_scores: PT_ROTATE trains and ranks one model, not universes");
+    PT_CHECK(model != PT_DISTMULT, PT_ENOTSUP,
+             "pt_lp_min_scores: PT_DISTMULT trains and ranks one model, not universes");
     PT_CHECK((us && pairs && d_key_rows) || n_pairs == 0, PT_EINVAL, "pt_lp_min_scores: null argument");
     if (n_pairs == 0) return PT_OK;
     hipStream_t st = (hipStream_t)stream;

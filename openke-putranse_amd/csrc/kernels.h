@@ -101,7 +101,7 @@ constexpr Shape pick_shape(int64_t D, bool vec4 = true) {
 }
 
 // instantiated (G, VEC, KCH) row shapes: float4 rows up to dim 1,024 (KCH 3 and 4: dims 516..1,024, TransE and TransH
-// and RotatE single models only; model_dim_supported is the rule), one-float rows up to dim 512
+// RotatE and DistMult single models only; model_dim_supported is the rule), one-float rows up to dim 512
 #define PT_SHAPES(X)                                                                                  \
     X(2, 4, 1) X(4, 4, 1) X(8, 4, 1) X(16, 4, 1) X(32, 4, 1) X(64, 4, 1) X(64, 4, 2) X(64, 4, 3)     \
     X(64, 4, 4)                                                                                       \
@@ -134,8 +134,8 @@ constexpr bool for_value(int v, F &&f) {
 
 // ---- kernels.hip: the dim rule and the score kernels
 // The one dim rule of the single-model path (pt_model_dim_supported answers it for models 0-2): dims 1..512 for every model (both row layouts
-// exist), dims 516..1,024 in multiples of 4 (float4 rows only) for TransE (0), TransH (1) and RotatE (3); nothing
-// else. RotatE's dim is its relation row's: an entity row is two such rows, re | im
+// exist), dims 516..1,024 in multiples of 4 (float4 rows only) for TransE (0), TransH (1), RotatE (3) and DistMult
+// (4); nothing else. RotatE's dim is its relation row's: an entity row is two such rows, re | im
 bool model_dim_supported(int64_t dim, int model);
 // dims at which both row layouts exist (1..512): what the one-float kernels (k_step_sampled, k_lp_scan_t's tile) take
 bool narrow_dim_supported(int64_t dim);
@@ -214,8 +214,12 @@ hipError_t launch_step_adv(const StepParams &P, const LossParams &L, const int64
                            const int64_t *br, const StepWorkspace &W, hipStream_t st);
 // every row of every table: gradient row (flagged rows only) -> normalize Jacobian -> Adam; block 0 reduces the
 // loss partials: loss (+)= loss_scale * sum(lpart) + loss_cst
+// l3 != 0 (DistMult's l3_regul_rate): 3 l3 x |x| joins every row's gradient and a second, one-block launch adds
+// l3 * sum |x|^3 over the pre-step tables to the loss from the per-block partials l3part[apply_adam_blocks(P)]
 hipError_t launch_apply_adam(const StepParams &P, const StepWorkspace &W, const AdamParams &A, int64_t bs,
-                             float loss_scale, float loss_cst, float *loss, hipStream_t st);
+                             float loss_scale, float loss_cst, float *loss, hipStream_t st, float l3 = 0.f,
+                             float *l3part = nullptr);
+int64_t apply_adam_blocks(const StepParams &P);
 // TransD (transd.hip): the external-batch step under plain MarginLoss (entity and transfer gradients finished in the
 // kernel, the relation's left in normalised space), and the scores; launch_score / launch_score_queries route model 2
 // to the latter two. The optimizer pass runs twice for TransD: (ent, rel), then transd_transfer_pass's view
@@ -259,6 +263,25 @@ inline StepParams rotate_half_rows(const StepParams &P) {
     Q.norm_flag = 0;
     return Q;
 }
+
+// DistMult (distmult.hip, model 4): tables laid out like TransE's, nothing normalised (the optimizer passes apply no
+// Jacobian). The external-batch step under SigmoidLoss with or without the adversarial weights (the score s = <h, r,
+// t> goes to the loss as it is: no model margin), with DistMult.regularization folded in; the scores -s behind
+// pt_score*; launch_score / launch_score_queries route model 4 to the latter two.
+// regul: regul_rate; l3: l3_regul_rate (the Adam pass's, launch_apply_adam); mode: how the data loader handed the
+// batch over (0 normal, 1 head_batch, 2 tail_batch), which decides what the regulariser's means run over
+struct RegulParams {
+    float regul = 0.f, l3 = 0.f;
+    int mode = 0;
+};
+int64_t step_distmult_max_neg(int64_t dim);
+hipError_t launch_step_distmult(const StepParams &P, const LossParams &L, const RegulParams &Rg, const int64_t *bh,
+                                const int64_t *bt, const int64_t *br, const StepWorkspace &W, hipStream_t st);
+hipError_t launch_score_distmult(const StepParams &P, int mode, const int64_t *h, const int64_t *t, const int64_t *r,
+                                 int64_t n, float *out, hipStream_t st);
+hipError_t launch_score_queries_distmult(const StepParams &P, int side, const int64_t *qh, const int64_t *qt,
+                                         const int64_t *qr, int64_t nq, int64_t E, float *out, hipStream_t st,
+                                         int global_order);
 
 hipError_t launch_torch_init(const pt_torch_init_job *d_jobs, int64_t n, hipStream_t st);
 hipError_t launch_rank_rows(const float *rows, int64_t E, const int64_t *row_of, const int64_t *truth,

@@ -26,22 +26,10 @@
 
 #include "device.h"
 #include "kernels.h"
+#include "loss_block.h"
 
 namespace pt {
 namespace dev {
-
-template <int G>
-__device__ __forceinline__ float gmax(float v) {
-#pragma unroll
-    for (int o = 1; o < G; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-// overflow-safe log(sigmoid(x)) and sigmoid(x)
-__device__ __forceinline__ float logsig(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
-__device__ __forceinline__ float sigm(float x) {
-    const float e = expf(-fabsf(x));
-    return (x >= 0.f ? 1.0f : e) / (1.0f + e);
-}
 
 struct AdvSink {   // (row_atomic: device.h)
     float *gent, *grel;
@@ -191,48 +179,7 @@ __global__ __launch_bounds__(256) void k_step_adv(StepParams P, LossParams L, co
         if (pass == 1) break;
         // ---- between the passes: weights, loss partial and dL/dd_k, lane-parallel over the group's scores
         __builtin_amdgcn_wave_barrier();   // LDS order inside a wave is program order
-        const float invB = 1.0f / (float)bs;
-        float zt = 0.f, ext = 0.f, winv = 1.0f / (float)neg;
-        if (L.adv) {
-            zt = L.kind == 1 ? L.temp : -L.temp;
-            float mx = -INFINITY;
-            for (int k = lane; k < neg; k += G) {
-                const float n = L.mflag ? L.gamma - sc[k] : sc[k];
-                mx = fmaxf(mx, zt > 0.f ? n : -n);
-            }
-            mx = gmax<G>(mx);
-            ext = zt > 0.f ? mx : -mx;   // the score of the largest weight: every exponent below is <= 0
-            float se = 0.f;
-            for (int k = lane; k < neg; k += G) {
-                const float n = L.mflag ? L.gamma - sc[k] : sc[k];
-                se += expf(zt * (n - ext));
-            }
-            winv = 1.0f / gsum<G>(se);
-        }
-        float lp = 0.f, cs = 0.f;
-        for (int k = lane; k < neg; k += G) {
-            const float n = L.mflag ? L.gamma - sc[k] : sc[k];
-            const float w = L.adv ? expf(zt * (n - ext)) * winv : winv;
-            float c;   // dL / dn_k
-            if (L.kind == 1) {
-                lp += w * logsig(-n);
-                c = w * sigm(n) * (0.5f * invB);
-            } else {
-                const float a = ps - n, m = P.margin;
-                lp += w * (a > -m ? a : -m);
-                const float hc = a > -m ? 1.0f : (a == -m ? 0.5f : 0.f);
-                cs += w * hc;
-                c = -(w * hc) * invB;
-            }
-            sc[k] = c * sg;
-        }
-        lp = gsum<G>(lp);
-        if (L.kind == 1) {
-            lp += logsig(ps);
-            dldp = -sigm(-ps) * (0.5f * invB);
-        } else {
-            dldp = gsum<G>(cs) * invB;
-        }
+        const float lp = loss_block<G>(L, P.margin, bs, neg, sc, lane, ps, sg, &dldp);   // (loss_block.h)
         if (lane == 0 && lpart) lpart[b] = lp;
         __builtin_amdgcn_wave_barrier();
     }

@@ -55,9 +55,13 @@ struct pt_trainer {
     pt::AdamParams adam{};
     bool adam_set = false;
     int64_t adam_step = 0;   // steps done
+    // DistMult's regularisers (pt_trainer_set_regul) and the Adam pass's per-block sum |x|^3 partials
+    pt::RegulParams regul{};
+    float *l3part = nullptr;
     // anything the in-kernel-sampled, captured and reference-order paths do not compute
     bool extended() const {
-        return !loss.plain() || P.opt == PT_ADAM || P.model == PT_TRANSD || P.model == PT_ROTATE;
+        return !loss.plain() || P.opt == PT_ADAM || P.model == PT_TRANSD || P.model == PT_ROTATE ||
+               P.model == PT_DISTMULT;
     }
     void drop_graphs() {
         for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
@@ -70,6 +74,7 @@ struct pt_trainer {
         if (csr_block) (void)hipFree(csr_block);
         if (W.lpart) (void)hipFree(W.lpart);
         if (ord_block) (void)hipFree(ord_block);
+        if (l3part) (void)hipFree(l3part);
     }
 };
 
@@ -351,7 +356,21 @@ static int enqueue_external(pt_trainer *t, int64_t bs, int64_t neg, const int64_
     float scale = P.inv_count, cst = P.margin;   // loss = scale * sum(lpart) + cst
     if (ev) PT_HIP(hipEventRecord(ev[0], st));
     const bool transd = P.model == PT_TRANSD;
-    if (P.model == PT_ROTATE) {
+    const float l3 = P.model == PT_DISTMULT ? t->regul.l3 : 0.f;
+    if (P.model == PT_DISTMULT) {
+        PT_CHECK(t->loss.kind == PT_LOSS_SIGMOID && !t->loss.mflag, PT_ENOTSUP,
+                 "PT_DISTMULT trains under PT_LOSS_SIGMOID on the raw score (pt_trainer_set_loss before the first "
+                 "step): PT_LOSS_MARGIN and a model margin are not implemented for it");
+        PT_CHECK(l3 == 0.f || adam, PT_ENOTSUP,
+                 "PT_DISTMULT: l3_regul_rate is dense and rides the PT_ADAM pass only (not PT_SGD / PT_ADAGRAD)");
+        PT_CHECK(neg <= pt::step_distmult_max_neg(P.dim), PT_ENOTSUP,
+                 "neg_ent " + std::to_string(neg) + " too large for the PT_DISTMULT step's LDS score buffer (max " +
+                     std::to_string(pt::step_distmult_max_neg(P.dim)) + ")");
+        if (l3 != 0.f && !t->l3part)   // (sized by the tables: allocated once)
+            PT_HIP(hipMalloc(&t->l3part, sizeof(float) * (size_t)pt::apply_adam_blocks(P)));
+        pt::loss_affine(t->loss, P, &scale, &cst);
+        PT_HIP(pt::launch_step_distmult(P, t->loss, t->regul, bh, bt, br, t->W, st));
+    } else if (P.model == PT_ROTATE) {
         PT_CHECK(t->loss.mflag, PT_ENOTSUP,
                  "PT_ROTATE scores gamma - d: pt_trainer_set_loss with score_margin_flag = 1 and the model's margin "
                  "must come before the first step");
@@ -382,7 +401,7 @@ static int enqueue_external(pt_trainer *t, int64_t bs, int64_t neg, const int64_
         const double step = (double)(t->adam_step + 1);
         A.step_size = (float)((double)P.lr / (1.0 - std::pow(A.beta1, step)));
         A.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(A.beta2, step));
-        PT_HIP(pt::launch_apply_adam(P, t->W, A, bs, scale, cst, d_loss, st));
+        PT_HIP(pt::launch_apply_adam(P, t->W, A, bs, scale, cst, d_loss, st, l3, t->l3part));
         if (transd) {   // the two transfer tables: a second pass with no loss (transd_transfer_pass)
             pt::StepParams P2;
             pt::StepWorkspace W2;
@@ -409,8 +428,8 @@ static int enqueue_external(pt_trainer *t, int64_t bs, int64_t neg, const int64_
 }
 
 static const char *kExtendedMsg =
-    "a non-default loss (pt_trainer_set_loss), PT_ADAM, PT_TRANSD and PT_ROTATE train external batches only: in-kernel "
-    "sampling, captured runs and the reference-order mode are not implemented for them";
+    "a non-default loss (pt_trainer_set_loss), PT_ADAM, PT_TRANSD, PT_ROTATE and PT_DISTMULT train external batches only: "
+    "in-kernel sampling, captured runs and the reference-order mode are not implemented for them";
 
 // per-positive loss partials for batches of up to `bs` positives (grown on demand, never during a
 // capture: callers prepare before enqueueing)
@@ -514,6 +533,7 @@ extern "C" int pt_trainer_set_deterministic(pt_trainer *t, int32_t on) {
     PT_CHECK(!on || pt::ordered_dim_supported(t->P.dim), PT_ENOTSUP, "reference-order mode: dim too large");
     PT_CHECK(!on || t->P.model != PT_TRANSD, PT_ENOTSUP, "reference-order mode is not implemented for TransD");
     PT_CHECK(!on || t->P.model != PT_ROTATE, PT_ENOTSUP, "reference-order mode is not implemented for PT_ROTATE");
+    PT_CHECK(!on || t->P.model != PT_DISTMULT, PT_ENOTSUP, "reference-order mode is not implemented for PT_DISTMULT");
     t->ordered = on != 0;
     return PT_OK;
 }
@@ -529,9 +549,27 @@ extern "C" int pt_trainer_set_loss(pt_trainer *t, const pt_loss_desc *l) {
     L.temp = l->adv ? l->temperature : 0.f;
     L.mflag = l->score_margin_flag ? 1 : 0;
     L.gamma = l->score_margin_flag ? l->score_margin : 0.f;
-    PT_CHECK(L.plain() || t->P.model == PT_TRANSE || t->P.model == PT_ROTATE, PT_ENOTSUP,
+    PT_CHECK(t->P.model != PT_DISTMULT || (L.kind == PT_LOSS_SIGMOID && !L.mflag), PT_ENOTSUP,
+             "PT_DISTMULT trains under PT_LOSS_SIGMOID on the raw score: PT_LOSS_MARGIN and score_margin_flag != 0 are "
+             "not implemented for it");
+    PT_CHECK(L.plain() || t->P.model == PT_TRANSE || t->P.model == PT_ROTATE || t->P.model == PT_DISTMULT, PT_ENOTSUP,
              "SigmoidLoss, adversarial weights and a model margin train TransE only (TransH is not implemented)");
     t->loss = L;
+    return PT_OK;
+}
+
+extern "C" int pt_trainer_set_regul(pt_trainer *t, const pt_regul_desc *r) {
+    PT_CHECK(t && r, PT_EINVAL, "pt_trainer_set_regul: null argument");
+    PT_CHECK(std::isfinite(r->regul_rate) && r->regul_rate >= 0.f && std::isfinite(r->l3_regul_rate) &&
+                 r->l3_regul_rate >= 0.f,
+             PT_EINVAL, "pt_trainer_set_regul: regul_rate and l3_regul_rate must be finite and >= 0");
+    PT_CHECK(r->batch_mode >= 0 && r->batch_mode <= 2, PT_EINVAL,
+             "pt_trainer_set_regul: batch_mode must be 0 (normal), 1 (head_batch) or 2 (tail_batch)");
+    PT_CHECK(t->P.model == PT_DISTMULT || (r->regul_rate == 0.f && r->l3_regul_rate == 0.f), PT_ENOTSUP,
+             "regul_rate and l3_regul_rate train PT_DISTMULT only");
+    t->regul.regul = r->regul_rate;
+    t->regul.l3 = r->l3_regul_rate;
+    t->regul.mode = r->batch_mode;
     return PT_OK;
 }
 

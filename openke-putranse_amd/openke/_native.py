@@ -20,7 +20,7 @@ c_u64p = ctypes.POINTER(ctypes.c_uint64)
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_f32p = ctypes.POINTER(ctypes.c_float)
 
-PT_TRANSE, PT_TRANSH, PT_TRANSD, PT_ROTATE = 0, 1, 2, 3
+PT_TRANSE, PT_TRANSH, PT_TRANSD, PT_ROTATE, PT_DISTMULT = 0, 1, 2, 3, 4
 PT_SGD, PT_ADAGRAD, PT_ADAM = 0, 1, 2
 PT_LOSS_MARGIN, PT_LOSS_SIGMOID = 0, 1
 PT_DETERMINISTIC = 1   # pt_universes_train_ex flag: reference-order (deterministic) mode
@@ -42,6 +42,11 @@ class ModelDesc(ctypes.Structure):
                 ("ent_transfer", c_vp), ("rel_transfer", c_vp), ("ent_transfer_acc", c_vp), ("rel_transfer_acc", c_vp),
                 # PT_ROTATE only: the phase divisor rel_embedding_range / pi
                 ("phase_div", c_f32)]
+
+
+class RegulDesc(ctypes.Structure):
+    """pt_regul_desc: DistMult's regularisers and how the batch was handed over (pt_trainer_set_regul)."""
+    _fields_ = [("regul_rate", c_f32), ("l3_regul_rate", c_f32), ("batch_mode", c_i32)]
 
 
 class LossDesc(ctypes.Structure):
@@ -123,6 +128,7 @@ SIGNATURES = {
     "pt_trainer_get_deterministic": (ctypes.c_int, [c_vp]),
     "pt_trainer_set_loss": (ctypes.c_int, [c_vp, ctypes.POINTER(LossDesc)]),
     "pt_trainer_set_adam": (ctypes.c_int, [c_vp, ctypes.POINTER(AdamState)]),
+    "pt_trainer_set_regul": (ctypes.c_int, [c_vp, ctypes.POINTER(RegulDesc)]),
     "pt_trainer_adam_step": (c_i64, [c_vp]),
     "pt_trainer_steps_timed": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "pt_trainer_sample_csr": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, ctypes.c_int32, c_vp,

@@ -11,7 +11,9 @@ corruption (neg_rel > 0) train batch by batch: GPU-sampled batch, then the exter
 TransE under SigmoidLoss, the self-adversarial weights (adv_temperature) or a model margin (k_step_adv),
 and Adam (k_apply_adam, dense) for either model, and every TransD step (k_step_transd: plain MarginLoss with SGD,
 Adagrad or Adam), and every RotatE step (k_step_rotate: SigmoidLoss or MarginLoss, with or without the adversarial
-weights, always on the model's margin; SGD, Adagrad or Adam)."""
+weights, always on the model's margin; SGD, Adagrad or Adam), and every DistMult step (k_step_distmult: SigmoidLoss or
+SoftplusLoss - the same function - with or without the adversarial weights; regul_rate inside the step kernel with any
+optimizer, l3_regul_rate inside the Adam pass)."""
 import ctypes
 import os
 
@@ -20,7 +22,7 @@ import torch
 from tqdm import tqdm
 
 from .. import _native
-from ..module.loss import MarginLoss, SigmoidLoss
+from ..module.loss import MarginLoss, SigmoidLoss, SoftplusLoss
 from ..module.model.Model import Model
 from ..module.strategy import NegativeSampling
 
@@ -64,6 +66,7 @@ class Trainer(object):
         self.checkpoint_dir = checkpoint_dir
         self._native = None
         self._native_key = None
+        self._regul_key = None   # (regul_rate, l3_regul_rate, batch mode) last given to pt_trainer_set_regul
         # reference-order mode (pt_trainer_set_deterministic): per-row gradient sums in slot order, lookup by
         # lookup, as embedding_dense_backward does (bit-identical run to run); off = the fused fast path
         self.deterministic = bool(deterministic)
@@ -76,14 +79,21 @@ class Trainer(object):
         kge, loss = ns.model, ns.loss
         if not isinstance(kge, Model) or kge.native_model is None:
             raise NotImplementedError("model %s is outside the accelerated path" % type(kge).__name__)
-        if not isinstance(loss, (MarginLoss, SigmoidLoss)):
+        distmult = kge.native_model == _native.PT_DISTMULT
+        if not isinstance(loss, (MarginLoss, SigmoidLoss)) and not (distmult and isinstance(loss, SoftplusLoss)):
             raise NotImplementedError("loss %s is outside the accelerated path (MarginLoss and SigmoidLoss are)"
                                       % type(loss).__name__)
-        if self._weighted(kge, loss) and kge.native_model not in (_native.PT_TRANSE, _native.PT_ROTATE):
+        if distmult and isinstance(loss, MarginLoss):
+            raise NotImplementedError("MarginLoss on DistMult is outside the accelerated path (it would minimise the "
+                                      "positive score): train DistMult under SigmoidLoss or SoftplusLoss")
+        if self._weighted(kge, loss) and kge.native_model not in (_native.PT_TRANSE, _native.PT_ROTATE,
+                                                                  _native.PT_DISTMULT):
             raise NotImplementedError("SigmoidLoss, adversarial temperature and a model margin are accelerated for "
                                       "TransE only")
-        if ns.regul_rate != 0 or ns.l3_regul_rate != 0:
+        if (ns.regul_rate != 0 or ns.l3_regul_rate != 0) and not distmult:
             raise NotImplementedError("regularisation is outside the accelerated path")
+        if not (ns.regul_rate >= 0 and ns.l3_regul_rate >= 0):
+            raise ValueError("regul_rate and l3_regul_rate must be >= 0")
         if self.lr_decay != 0 or self.weight_decay != 0:
             raise NotImplementedError("lr_decay / weight_decay are 0 in the reference path")
         return ns, kge, loss
@@ -91,7 +101,8 @@ class Trainer(object):
     @staticmethod
     def _weighted(kge, loss):
         """Whether the step is outside plain MarginLoss on the raw distance (then k_step_adv computes it)."""
-        return isinstance(loss, SigmoidLoss) or bool(loss.adv_flag) or bool(getattr(kge, "margin_flag", False))
+        return (isinstance(loss, (SigmoidLoss, SoftplusLoss)) or bool(loss.adv_flag)
+                or bool(getattr(kge, "margin_flag", False)))
 
     def _setup(self):
         _native.require_gpu()
@@ -112,6 +123,11 @@ class Trainer(object):
         weighted = self._weighted(kge, loss)
         if self.deterministic and kge.native_model == _native.PT_ROTATE:
             raise NotImplementedError("deterministic=True (reference-order mode) is not implemented for RotatE")
+        if self.deterministic and kge.native_model == _native.PT_DISTMULT:
+            raise NotImplementedError("deterministic=True (reference-order mode) is not implemented for DistMult")
+        if ns.l3_regul_rate != 0 and opt.method != _native.PT_ADAM:
+            raise NotImplementedError("l3_regul_rate is dense: it is accelerated with Adam only (opt_method %r would "
+                                      "make a sparse pass dense)" % (self.opt_method,))
         if self.deterministic and (weighted or opt.method == _native.PT_ADAM):
             raise NotImplementedError("deterministic=True (reference-order mode) covers plain MarginLoss with SGD or "
                                       "Adagrad only")
@@ -130,7 +146,9 @@ class Trainer(object):
         self._native_key = key
         _native.check(L.pt_trainer_set_deterministic(self._native, 1 if self.deterministic else 0))
         ld = _native.LossDesc()
-        ld.kind = _native.PT_LOSS_SIGMOID if isinstance(loss, SigmoidLoss) else _native.PT_LOSS_MARGIN
+        # (SoftplusLoss.py:22-26 is SigmoidLoss's function: softplus(x) = -logsigmoid(-x), the threshold moves 2e-9)
+        ld.kind = (_native.PT_LOSS_SIGMOID if isinstance(loss, (SigmoidLoss, SoftplusLoss))
+                   else _native.PT_LOSS_MARGIN)
         ld.adv = 1 if loss.adv_flag else 0
         ld.temperature = float(loss.adv_temperature.item()) if loss.adv_flag else 0.0
         ld.score_margin_flag = 1 if getattr(kge, "margin_flag", False) else 0
@@ -147,12 +165,27 @@ class Trainer(object):
             a.eps = opt.eps
             a.step = int(opt.step)
             _native.check(L.pt_trainer_set_adam(self._native, ctypes.byref(a)))
+        self._regul_key = None
+        self._set_regul(ns, kge, 0)
         return ns, kge, loss
+
+    def _set_regul(self, ns, kge, mode):
+        """DistMult's regularisers and how the step's batch was handed over (0 normal, 1 head_batch, 2 tail_batch):
+        pt_trainer_set_regul, called when either changes (cross sampling alternates the mode per step)."""
+        if kge.native_model != _native.PT_DISTMULT:
+            return
+        key = (float(ns.regul_rate), float(ns.l3_regul_rate), int(mode))
+        if key == self._regul_key:
+            return
+        rd = _native.RegulDesc()
+        rd.regul_rate, rd.l3_regul_rate, rd.batch_mode = key
+        _native.check(_native.lib().pt_trainer_set_regul(self._native, ctypes.byref(rd)))
+        self._regul_key = key
 
     def _external_only(self, kge, loss):
         """Whether every step goes through the external-batch step (k_step / k_step_adv + k_apply / k_apply_adam)."""
         return (self._weighted(kge, loss) or self.optimizer.method == _native.PT_ADAM
-                or kge.native_model in (_native.PT_TRANSD, _native.PT_ROTATE))
+                or kge.native_model in (_native.PT_TRANSD, _native.PT_ROTATE, _native.PT_DISTMULT))
 
     def _sync_step(self):
         if self.optimizer.method == _native.PT_ADAM:
@@ -191,6 +224,7 @@ class Trainer(object):
             else:
                 h = h[:bs].repeat(rep)
             r = r[:bs].repeat(rep)
+        self._set_regul(ns, kge, {'normal': 0, 'head_batch': 1, 'tail_batch': 2}[mode])
         n = h.numel()
         if n % bs != 0 or n // bs < 2:
             raise ValueError("batch of %d triples does not match batch_size %d with negatives" % (n, bs))
@@ -202,7 +236,7 @@ class Trainer(object):
         self._sync_step()
         return out.item()
 
-    def _run_batches(self, L, sampler, bern, bs, nb, losses, buf):
+    def _run_batches(self, L, sampler, bern, bs, nb, losses, buf, ns=None, kge=None):
         """One epoch of device-sampled batches outside the fused form - cross sampling (the loader's
         __iter__ alternates tail_batch / head_batch, TrainDataLoader.py:240-246, 320-324) or relation
         corruption (neg_rel > 0): every batch is drawn by the GPU sampler into device arrays (k_sample,
@@ -226,6 +260,8 @@ class Trainer(object):
                 fixed = t if mode == -1 else h
                 fixed.view(-1, bs)[1:] = fixed[:bs]
                 r.view(-1, bs)[1:] = r[:bs]
+            if kge is not None:   # (mode -1: t is the fixed side, head_batch)
+                self._set_regul(ns, kge, 0 if mode == 0 else (1 if mode == -1 else 2))
             _native.check(L.pt_trainer_step(self._native, None, bs, neg + neg_rel, 0, 0, _native.ptr(h),
                                             _native.ptr(t), _native.ptr(r), _native.ptr(losses[i:i + 1]), st))
 
@@ -261,7 +297,7 @@ class Trainer(object):
                                                _native.ptr(losses), _native.stream()))
             elif nb > 0:
                 losses.zero_()
-                self._run_batches(L, sampler, bern, bs, nb, losses, buf)
+                self._run_batches(L, sampler, bern, bs, nb, losses, buf, ns, kge)
                 self._sync_step()
             host = losses.cpu().numpy()
             self.last_step_losses = host[:nb].copy()

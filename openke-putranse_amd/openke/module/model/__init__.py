@@ -5,5 +5,6 @@ from .TransE import TransE
 from .TransH import TransH
 from .TransD import TransD
 from .RotatE import RotatE
+from .DistMult import DistMult
 
-__all__ = ['Model', 'TransE', 'TransH', 'TransD', 'RotatE']
+__all__ = ['Model', 'TransE', 'TransH', 'TransD', 'RotatE', 'DistMult']
