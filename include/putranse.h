@@ -135,7 +135,7 @@ int pt_trainer_run(pt_trainer *t, pt_sampler *sampler, int64_t bs, int64_t neg, 
                    int64_t steps, float *d_losses, void *stream);
 /* 1 when pt_trainer_run takes batches of bs x neg on this trainer (its model, dim, loss, optimizer and mode), else 0:
  * the caller then trains the same batches one by one (pt_sampler_sample_ex + pt_trainer_step on external batches).
- * At dims above 512 the fused run exists for TransE with neg >= 4 while the entity, relation and bs * neg
+ * At dims above 512 the fused run exists for TransE with neg >= 4 while the entity, relation and bs * (neg + 3)
  * contribution rows stay under 2^31 bytes, and for the reference-order mode. No device call. */
 int pt_trainer_fused_supported(const pt_trainer *t, int64_t bs, int64_t neg);
 
@@ -144,6 +144,16 @@ int pt_trainer_fused_supported(const pt_trainer *t, int64_t bs, int64_t neg);
  * sampler); parts = workgroups per call of the split sampler (0 = automatic, ceil(512 / calls)). Every path
  * draws the same batches (bit-exact); this selects only how. */
 int pt_trainer_set_sampling(pt_trainer *t, int32_t path, int64_t parts);
+/* Stored positive rows of the large-neg TransE step (k_step_csr + k_apply_buf). Per step, the first ent_cap uses of
+ * an entity row and the first rel_cap uses of a relation row by the step's positives (as h / t, as r) get a
+ * contribution row of their own: the step kernel stores the gradient there with plain stores and the apply pass sums
+ * the row's bucket; uses beyond the cap add into the table's gradient row with float atomics, as every use did
+ * before. -1 selects the library's choice, 0 / 0 the all-atomic behaviour. A parameter, not a mode: the kernels are
+ * the same for every value and the results differ only in the order of the float sums. Where the pair above does not
+ * run (TransH, dims that are no multiple of 4, tables beyond 2^31 bytes, more table rows than k_pos_slots' LDS
+ * holds) the caps read as set but nothing is stored. Synchronizes the device and drops captured epochs. */
+int pt_trainer_set_positive_caps(pt_trainer *t, int32_t ent_cap, int32_t rel_cap);
+int pt_trainer_positive_caps(const pt_trainer *t, int32_t *ent_cap, int32_t *rel_cap);
 /* Compatibility shim of the removed two-launch split sampling (a chunk's first `head` steps sampled ahead, the rest
  * on a side stream; measured slower and removed: DESIGN.md section 4). The setter accepts head = 0 or -1 (PT_OK) and
  * answers PT_ENOTSUP to head > 0 (PT_EINVAL for a null trainer or head < -1). */
@@ -216,7 +226,7 @@ int pt_trainer_steps_timed(pt_trainer *t, int64_t bs, int64_t neg, const int64_t
 
 /* Measurement hook: `steps` in-kernel-sampled steps launched one by one (no graph) with an event pair
  * around every launch on `stream`. ms4[k] = total duration of kernel kind k divided by `steps`:
- * 0 batch sampling (k_sample_csr, large-neg path only, one launch per chunk of steps), 1 bucket scan
+ * 0 batch sampling (k_sample_csr, large-neg path only, one launch per chunk of steps, and k_pos_slots), 1 bucket scan
  * (k_scan_counts, idem), 2 fused forward/backward (k_step_csr / k_step_sampled), 3 sparse optimizer
  * (k_apply_buf / k_apply). On the large-neg path kinds 2 and 3 are then re-timed back to back (one
  * event pair per loop of `steps` launches on the last sampled batch; tables, optimizer state and
@@ -250,6 +260,13 @@ int pt_trainer_slot_scale(const pt_trainer *t);
 int pt_trainer_sample_csr(pt_trainer *t, pt_sampler *sampler, int64_t bs, int64_t neg, int64_t bern, int64_t filter,
                           int64_t calls, int32_t path, int32_t *h_pos, int32_t *h_neg, int32_t *h_dst,
                           int32_t *h_start, void *stream);
+/* The positives' stored rows of the chunk pt_trainer_sample_csr sampled last (`calls` of its calls), copied to HOST
+ * arrays (synchronizes): h_pdst [calls][bs][3] = the contribution rows of each positive's h, r and t gradients, or
+ * -1 where the use ranked at or beyond its row's cap; h_pstart [calls][ent_total + rel_total + 1] = the starts of
+ * the rows' buckets (entity e at [e], relation r at [ent_total + r]), offset by the bs * neg rows of the negatives.
+ * *stored = 1 when this (bs, neg) takes the stored path at all. */
+int pt_trainer_positive_slots(pt_trainer *t, int64_t calls, int32_t *h_pdst, int32_t *h_pstart, int32_t *stored,
+                              void *stream);
 
 /* ------------------------------------------------------------------ scoring ------------------ */
 /* scores = ||h + r - t||_p as model.predict computes them (TransE.py:46-74, TransH.py:52-93, TransD.py:94-129):

@@ -31,7 +31,8 @@ struct ApplyTable {
     int64_t rows;
     int jacobian;
     const int *start;       // CSR of extra contribution rows (NULL: none): rows start[r] .. start[r+1]-1
-    const float *contrib;   // [n][dim]
+    const int *pstart;      // a second bucket of contribution rows, the positives' stored rows (CsrWork::pstart;
+                            // NULL: none): rows pstart[r] .. pstart[r+1]-1, summed after the first bucket's
 };
 struct ApplyParams {
     ApplyTable t[3];
@@ -46,6 +47,7 @@ struct ApplyParams {
     const float *lpart;   // [bs] per-positive loss partials of the step
     float margin, inv_count;
     int loss_assign;
+    const float *contrib;   // [n][dim] the contribution rows both buckets index (NULL: none)
 };
 
 // block 0, first wave: advance the sampler streams and reduce the step's loss partials in a fixed
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(256) void k_apply(ApplyParams A) {
     for (; j + 4 <= c1; j += 4) {
         Vec c[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) vload(c[u], T.contrib + (int64_t)(j + u) * D, D, lane);
+        for (int u = 0; u < 4; ++u) vload(c[u], A.contrib + (int64_t)(j + u) * D, D, lane);
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(256) void k_apply(ApplyParams A) {
     }
     for (; j < c1; ++j) {
         Vec c;
-        vload(c, T.contrib + (int64_t)j * D, D, lane);
+        vload(c, A.contrib + (int64_t)j * D, D, lane);
 #pragma unroll
         for (int i = 0; i < Vec::N; ++i) gsum_.x[i] += c.x[i];
     }
@@ -144,7 +146,9 @@ __global__ __launch_bounds__(256) void k_apply(ApplyParams A) {
 // group per table row. The row (and its Adagrad state) load is issued before the flag / bucket range
 // loads return; a bucket's contribution rows stream NC at a time with out-of-range offsets past its
 // end (the hardware returns zeros, so the adds need no branches), summed in bucket order after the
-// row's own gradient row.
+// row's own gradient row. A row has up to two buckets, read as one stream: the negatives' counting-sort rows
+// (entity table) and the positives' stored rows (entity and relation tables, at most the cap long); its
+// gradient row is loaded, re-zeroed and un-flagged only when flagged (the uses beyond the cap).
 template <int G, int VEC, int KCH, int NC>
 __global__ __launch_bounds__(256) void k_apply_buf(ApplyParams A) {
     using Vec = V<G, VEC, KCH>;
@@ -162,7 +166,7 @@ __global__ __launch_bounds__(256) void k_apply_buf(ApplyParams A) {
         ++ti;
     }
     const bool live = ti < A.ntab;
-    int flag = 0, c0 = 0, c1 = 0;
+    int flag = 0, c0 = 0, c1 = 0, p0 = 0, p1 = 0;
     Vec x, g, a;
     // (the one-trip loops keep the instruction stream of the former rows-per-group loops: DESIGN.md §4)
     // ---- every load of the row in flight together
@@ -178,23 +182,31 @@ __global__ __launch_bounds__(256) void k_apply_buf(ApplyParams A) {
             c0 = T.start[row];
             c1 = T.start[row + 1];
         }
+        if (T.pstart) {
+            p0 = T.pstart[row];
+            p1 = T.pstart[row + 1];
+        }
     }
-    int len = 0;
+    int len = 0, n0 = 0;
 #pragma unroll
     for (int once = 0; once < 1; ++once) {
         if (!live) continue;
         const ApplyTable &T = A.t[ti];
         bload(g, make_rsrc(T.grad, (uint32_t)T.rows * rowb), flag ? (uint32_t)row * rowb : kOob, D, lane);
-        len = c1 - c0 > len ? c1 - c0 : len;
+        n0 = c1 - c0;
+        len = n0 + (p1 - p0);
     }
-    // ---- contribution rows (entity table only): the row's bucket streamed NC at a time, out-of-range past
-    // the bucket's end (zeros), summed in bucket order
-    const auto c_rs = make_rsrc(A.t[0].contrib, 0x7fffffffu);
+    // ---- contribution rows: the row's buckets streamed NC at a time, out-of-range past their end (zeros),
+    // summed in bucket order, the negatives' bucket first
+    const auto c_rs = make_rsrc(A.contrib, 0x7fffffffu);
     for (int j = 0; j < len; j += NC) {
         Vec c[NC];
 #pragma unroll
-        for (int q = 0; q < NC; ++q)
-            bload(c[q], c_rs, c0 + j + q < c1 ? (uint32_t)(c0 + j + q) * rowb : kOob, D, lane);
+        for (int q = 0; q < NC; ++q) {
+            const int i = j + q;
+            const int r = i < n0 ? c0 + i : p0 + (i - n0);
+            bload(c[q], c_rs, i < len ? (uint32_t)r * rowb : kOob, D, lane);
+        }
 #pragma unroll
         for (int q = 0; q < NC; ++q)
 #pragma unroll
@@ -203,7 +215,7 @@ __global__ __launch_bounds__(256) void k_apply_buf(ApplyParams A) {
     // ---- the update
 #pragma unroll
     for (int once = 0; once < 1; ++once) {
-        if (!live || (!flag && c0 == c1)) continue;   // untouched row: unchanged
+        if (!live || (!flag && len == 0)) continue;   // untouched row: unchanged
         const ApplyTable &T = A.t[ti];
         const uint32_t tb = (uint32_t)T.rows * rowb;
         Vec gg;
@@ -243,11 +255,17 @@ hipError_t launch_apply(const StepParams &P, const StepWorkspace &W, uint64_t *s
     dev::ApplyParams A{};
     A.ntab = 0;
     const int ent_j = P.model == 0 && P.norm_flag;
-    A.t[A.ntab++] = dev::ApplyTable{P.ent, P.ent_acc, W.gent, W.fent, P.ent_total, ent_j,
-                                    csr ? csr->start : nullptr, csr ? csr->contrib : nullptr};
-    A.t[A.ntab++] = dev::ApplyTable{P.rel, P.rel_acc, W.grel, W.frel, P.rel_total, P.norm_flag, nullptr, nullptr};
+    // on a counting-sort batch the relation rows come first in the grid: their buckets of stored positive rows
+    // are the longest (up to the relation cap), so they must not be the kernel's tail
+    const dev::ApplyTable ent{P.ent, P.ent_acc, W.gent, W.fent, P.ent_total, ent_j, csr ? csr->start : nullptr,
+                              csr ? csr->pstart : nullptr};
+    const dev::ApplyTable rel{P.rel, P.rel_acc, W.grel, W.frel, P.rel_total, P.norm_flag, nullptr,
+                              csr && csr->pstart ? csr->pstart + P.ent_total : nullptr};
+    A.t[A.ntab++] = csr ? rel : ent;
+    A.t[A.ntab++] = csr ? ent : rel;
     if (P.model == 1)
         A.t[A.ntab++] = dev::ApplyTable{P.normv, P.norm_acc, W.gnorm, W.fnorm, P.rel_total, 1, nullptr, nullptr};
+    A.contrib = csr ? csr->contrib : nullptr;
     A.dim = P.dim;
     A.opt = P.opt;
     A.lr = P.lr;
@@ -264,7 +282,7 @@ hipError_t launch_apply(const StepParams &P, const StepWorkspace &W, uint64_t *s
     for (int i = 0; i < A.ntab; ++i) rows += A.t[i].rows;
     // float4 rows through raw buffers (k_apply_buf) where the offsets fit 31 bits - the contribution rows count
     // only when there are any - else k_apply
-    const bool buf = P.dim % 4 == 0 && offsets_fit31(P, csr ? P.batch_size * P.neg : 0);
+    const bool buf = P.dim % 4 == 0 && offsets_fit31(P, csr ? csr_con_rows(P.batch_size, P.neg) : 0);
     const int64_t gpb = 256 / s.G;
     const dim3 grid((unsigned)((rows + gpb - 1) / gpb)), block(256);
     hipError_t e = hipErrorInvalidValue;

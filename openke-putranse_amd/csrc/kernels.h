@@ -52,6 +52,12 @@ struct CsrWork {
     int32_t *tick = nullptr;    // [calls + 1] parts of a call done, then calls done (k_sample_part; zero between uses)
     int rank_only = 0;          // off[] holds bucket ranks (k_sample_part) instead of destinations
     int64_t cnt_stride = 0, start_stride = 0;
+    // stored positive rows (k_pos_slots): the first `cap` uses of a table row by a step's positives get a row of
+    // `contrib` after the bs*neg rows of the negatives; later uses keep the float atomics
+    int4 *pdst = nullptr;       // [calls][bs] contrib rows of the positive's (h, r, t) gradients, -1 = atomic path
+    int32_t *pstart = nullptr;  // [calls][pstart_stride] starts of the rows' clipped buckets: entity e at [e],
+                                // relation r at [ent_total + r]; ent_total + rel_total + 1 used
+    int64_t pstart_stride = 0;
 };
 
 inline CsrWork csr_view(const CsrWork &w, int64_t call, int64_t bs, int64_t neg) {
@@ -61,6 +67,8 @@ inline CsrWork csr_view(const CsrWork &w, int64_t call, int64_t bs, int64_t neg)
     v.off = w.off + call * bs * neg;
     v.cnt = w.cnt + call * w.cnt_stride;
     v.start = w.start + call * w.start_stride;
+    v.pdst = w.pdst + call * bs;
+    v.pstart = w.pstart + call * w.pstart_stride;
     return v;
 }
 
@@ -174,11 +182,21 @@ bool sample_part_fits(int64_t bs, int64_t neg, int64_t n, int64_t parts);
 bool sample_part_prepare(int64_t bs, int64_t neg, int64_t n, int64_t parts);
 hipError_t launch_scan_counts(const CsrWork &w, int64_t n, int64_t calls, uint64_t *states, int64_t threads,
                               int64_t bs, int64_t dpp, hipStream_t st);
+// the positives' stored gradient rows of `calls` steps (k_pos_slots, one workgroup per step): counts every row's uses
+// by the step's positives in LDS, clips them at ent_cap / rel_cap and writes pdst / pstart; reads w.pos only.
+// pos_slots_prepare: whether its LDS plan fits (raises the kernel's LDS limit: call outside any stream capture)
+bool pos_slots_prepare(int64_t bs, int64_t neg, int64_t ent_total, int64_t rel_total);
+hipError_t launch_pos_slots(const CsrWork &w, int64_t bs, int64_t neg, int64_t ent_total, int64_t rel_total,
+                            int ent_cap, int rel_cap, int64_t calls, hipStream_t st);
 // the raw-buffer kernels (k_step_csr, k_apply_buf) address the ent / rel tables and con_rows contribution rows with
 // byte offsets that must fit 31 bits
 inline bool offsets_fit31(const StepParams &P, int64_t con_rows) {
     return (P.ent_total + P.rel_total + con_rows) * P.dim * 4 < (int64_t(1) << 31);
 }
+// contribution rows of a counting-sort step: one per negative slot and three per positive (CsrWork::pdst)
+inline int64_t csr_con_rows(int64_t bs, int64_t neg) { return bs * (neg + 3); }
+// whether launch_step takes k_step_csr on a counting-sort batch (then launch_apply takes k_apply_buf)
+bool csr_fast_path(const StepParams &P);
 bool step_fits(const StepParams &P, int64_t neg, bool csr);
 hipError_t launch_step(const StepParams &P, const DeviceGraph &g, const uint64_t *states, int64_t threads, int bern,
                        int filter, const int64_t *bh, const int64_t *bt, const int64_t *br, const StepWorkspace &W,

@@ -566,6 +566,88 @@ __global__ __launch_bounds__(1024) void k_scan_counts(int32_t *__restrict__ cnt_
     for (int64_t i = tid; i < slots; i += 1024) off[i] = start[neg[i] >> 1] + off[i];
 }
 
+// Stored rows for the positives' gradients (one workgroup of 1024 threads per sampled step, all in LDS; reads
+// w.pos only, after any of the three samplers). Every positive uses three table rows: entity rows h and t and
+// relation row r (row n_ent + r of the combined index). A use's rank in its row is reserved with an LDS atomic;
+// the first `cap` uses of a row (ent_cap / rel_cap by table) get a contribution row of their own, the step
+// kernel stores the gradient there and the apply pass sums the row's bucket; later uses keep the float atomics
+// (pdst -1), so no bucket grows past its cap whatever the graph. The clipped counts are scanned like
+// k_scan_counts' (tiles of 16,384: 16 contiguous counts per thread) into pstart[], offset by `base` = the
+// negatives' bs * neg rows of the same contribution array.
+__global__ __launch_bounds__(1024) void k_pos_slots(CsrWork w, int64_t bs, int32_t base, int32_t n_ent,
+                                                    int32_t n_rows, int32_t ent_cap, int32_t rel_cap) {
+    extern __shared__ int32_t s_use[];   // [n_rows] uses of a row, then the start of its clipped bucket
+    __shared__ int32_t wtot[16];
+    __shared__ int32_t carry_s;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int4 *pos = w.pos + (int64_t)blockIdx.x * bs;
+    int4 *pdst = w.pdst + (int64_t)blockIdx.x * bs;
+    int32_t *pstart = w.pstart + (int64_t)blockIdx.x * w.pstart_stride;
+    for (int32_t i = tid; i < n_rows; i += 1024) s_use[i] = 0;
+    if (tid == 0) carry_s = 0;
+    __syncthreads();
+    // ---- every use's rank in its row (parked in pdst: the thread that wrote a record reads it back below)
+    for (int64_t b = tid; b < bs; b += 1024) {
+        const int4 q = pos[b];
+        const int32_t kh = atomicAdd(&s_use[q.x], 1);
+        const int32_t kr = atomicAdd(&s_use[n_ent + q.y], 1);
+        const int32_t kt = atomicAdd(&s_use[q.z], 1);
+        pdst[b] = make_int4(kh, kr, kt, 0);
+    }
+    __syncthreads();
+    // ---- exclusive scan of min(uses, cap), in place
+    for (int32_t tile = 0; tile < n_rows; tile += 16384) {
+        const int32_t lo = tile + tid * 16;
+        int32_t v[16];
+        int32_t tsum = 0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int32_t i = lo + q;
+            const int32_t cap = i < n_ent ? ent_cap : rel_cap;
+            const int32_t c = i < n_rows ? s_use[i] : 0;
+            v[q] = c < cap ? c : cap;
+            tsum += v[q];
+        }
+        int32_t incl = tsum;   // inclusive wave scan of the thread totals
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int32_t y = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += y;
+        }
+        if (lane == 63) wtot[wid] = incl;
+        __syncthreads();
+        int32_t wpre = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int32_t t = wtot[k];
+            wpre += k < wid ? t : 0;
+            total += t;
+        }
+        int32_t run = carry_s + wpre + incl - tsum;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int32_t i = lo + q;
+            if (i < n_rows) {
+                s_use[i] = run;
+                pstart[i] = base + run;
+            }
+            run += v[q];
+        }
+        __syncthreads();
+        if (tid == 0) carry_s += total;
+        __syncthreads();
+    }
+    if (tid == 0) pstart[n_rows] = base + carry_s;
+    // ---- ranks -> contribution rows
+    for (int64_t b = tid; b < bs; b += 1024) {
+        const int4 q = pos[b];
+        const int4 k = pdst[b];
+        pdst[b] = make_int4(k.x < ent_cap ? base + s_use[q.x] + k.x : -1,
+                            k.y < rel_cap ? base + s_use[n_ent + q.y] + k.y : -1,
+                            k.z < ent_cap ? base + s_use[q.z] + k.z : -1, 0);
+    }
+}
+
 }  // namespace dev
 
 // ==================================================================== host launchers ===========
@@ -671,6 +753,25 @@ hipError_t launch_sample_part(const DeviceGraph &g, uint64_t *states, int64_t th
     PT_PART(true, 2) PT_PART(true, 4) PT_PART(false, 2) PT_PART(false, 4)
 #undef PT_PART
     return hipErrorInvalidValue;
+}
+
+// k_pos_slots keeps one count per entity and relation row in LDS
+static size_t pos_slots_lds(int64_t ent_total, int64_t rel_total) { return 4 * (size_t)(ent_total + rel_total); }
+
+bool pos_slots_prepare(int64_t bs, int64_t neg, int64_t ent_total, int64_t rel_total) {
+    if (pos_slots_lds(ent_total, rel_total) > kSampleSortLds || csr_con_rows(bs, neg) >= (int64_t(1) << 30)) return false;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(dev::k_pos_slots),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSampleSortLds) == hipSuccess;
+}
+
+hipError_t launch_pos_slots(const CsrWork &w, int64_t bs, int64_t neg, int64_t ent_total, int64_t rel_total,
+                            int ent_cap, int rel_cap, int64_t calls, hipStream_t st) {
+    const size_t lds = pos_slots_lds(ent_total, rel_total);
+    if (lds > kSampleSortLds || ent_total + rel_total + 1 > w.pstart_stride || !w.pdst || !w.pstart)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dev::k_pos_slots, dim3((unsigned)calls), dim3(1024), lds, st, w, bs, (int32_t)(bs * neg),
+                       (int32_t)ent_total, (int32_t)(ent_total + rel_total), (int32_t)ent_cap, (int32_t)rel_cap);
+    return hipGetLastError();
 }
 
 hipError_t launch_scan_counts(const CsrWork &w, int64_t n, int64_t calls, uint64_t *states, int64_t threads,

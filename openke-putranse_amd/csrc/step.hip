@@ -321,7 +321,9 @@ __global__ __launch_bounds__(256) void k_step_sampled(StepParams P, DeviceGraph 
 // base h-hat + r-hat is formed once (same association as (h + r) - t), the corrupted row's gradient is
 // formed with the sign of its slot and stored to its counting-sort slot, and two accumulators collect
 // the positive's rows: At = sum over tail-corrupted negatives of dL/dv, Ah over head-corrupted ones
-// (dL/dh-hat = At + g+, dL/dr-hat = At + Ah + g+, dL/dt-hat = -(Ah + g+)).
+// (dL/dh-hat = At + g+, dL/dr-hat = At + Ah + g+, dL/dt-hat = -(Ah + g+)). Each of these three rows goes to the
+// contribution row k_pos_slots reserved for it (CsrWork::pdst, a plain float4 store like a negative's), or, where
+// the use ranked beyond its table row's cap (-1), into the table's gradient row with float atomics.
 template <int G>
 __device__ __forceinline__ int32_t gbcast(int32_t v, int j) {
     if constexpr (G == 64) return __builtin_amdgcn_readlane(v, j); else return __shfl(v, j, G);
@@ -354,12 +356,17 @@ __global__ __launch_bounds__(NT) void k_step_csr(StepParams P, GlobalSink sink, 
     vzero(At); vzero(Ah); vzero(rh); vzero(th); vzero(bt);
     float csum = 0.f, lsum = 0.f, ps = 0.f;
     int32_t hp = 0, rp = 0, tp = 0;
+    int32_t dh = -1, dr = -1, dt = -1;   // contribution rows of the positive's h, r, t gradients (-1: atomics)
+    // (the negatives' bs * neg rows, then the positives' stored rows: csr_con_rows)
+    const uint32_t conb = (uint32_t)(P.batch_size * (neg + 3)) * rowb;
     if (active) {
         const auto ent_rs = make_rsrc(P.ent, (uint32_t)P.ent_total * rowb);
         const auto rel_rs = make_rsrc(P.rel, (uint32_t)P.rel_total * rowb);
-        const auto con_rs = make_rsrc(cw.contrib, (uint32_t)(P.batch_size * neg) * rowb);
+        const auto con_rs = make_rsrc(cw.contrib, conb);
         const int4 q = cw.pos[b];
+        const int4 qd = cw.pdst[b];   // ready-made destinations, in flight with the positive's record
         hp = uni<G>(q.x); rp = uni<G>(q.y); tp = uni<G>(q.z);
+        dh = uni<G>(qd.x); dr = uni<G>(qd.y); dt = uni<G>(qd.z);
         const int32_t *nrec = cw.neg + b * neg;
         const int32_t *ndst = cw.off + b * neg;
         int w0 = k_lo, wend = k_hi - k_lo < G ? k_hi : k_lo + G;
@@ -490,7 +497,15 @@ __global__ __launch_bounds__(NT) void k_step_csr(StepParams P, GlobalSink sink, 
     }
     if (!active) return;
     if (lane == 0 && sink.lpart) sink.lpart[b] = lsum;
-    if (uni<G>(csum) == 0.f) return;   // no active pair: every accumulator is zero
+    const auto con_rs = make_rsrc(cw.contrib, conb);
+    if (uni<G>(csum) == 0.f) {   // no active pair: every accumulator is zero, but a reserved row must be defined
+        Vec z;
+        vzero(z);
+        if (dr >= 0) bstore(z, con_rs, (uint32_t)dr * rowb, D, lane);
+        if (dh >= 0) bstore(z, con_rs, (uint32_t)dh * rowb, D, lane);
+        if (dt >= 0) bstore(z, con_rs, (uint32_t)dt * rowb, D, lane);
+        return;
+    }
     Vec gv, aH, aR, aT, vpos;
 #pragma unroll
     for (int i = 0; i < Vec::N; ++i) vpos.x[i] = bt.x[i] - th.x[i];
@@ -501,15 +516,21 @@ __global__ __launch_bounds__(NT) void k_step_csr(StepParams P, GlobalSink sink, 
         aR.x[i] = (At.x[i] + Ah.x[i]) + gv.x[i];
         aT.x[i] = -(Ah.x[i] + gv.x[i]);
     }
-    // float4 lanes make a row atomic touch 4x the cache lines per instruction: pass the three rows
+    // a row with a stored destination (group-uniform branches): its float4 row goes straight to its slot
+    if (dr >= 0) bstore(aR, con_rs, (uint32_t)dr * rowb, D, lane);
+    if (dh >= 0) bstore(aH, con_rs, (uint32_t)dh * rowb, D, lane);
+    if (dt >= 0) bstore(aT, con_rs, (uint32_t)dt * rowb, D, lane);
+    if (dr >= 0 && dh >= 0 && dt >= 0) return;
+    // the uses beyond a row's cap: float atomics into the gradient row, and its flag.
+    // float4 lanes make a row atomic touch 4x the cache lines per instruction: pass the rows
     // through LDS so lane l adds floats l, l + G, ... (256 contiguous bytes per instruction at G = 64)
     float *tb = trb + (grp / S) * 3 * RW;
 #pragma unroll
     for (int k = 0; k < Vec::N; ++k) {
         const int c = ((k / VEC) * G + lane) * VEC + k % VEC;
-        tb[c] = aR.x[k];
-        tb[RW + c] = aH.x[k];
-        tb[2 * RW + c] = aT.x[k];
+        if (dr < 0) tb[c] = aR.x[k];
+        if (dh < 0) tb[RW + c] = aH.x[k];
+        if (dt < 0) tb[2 * RW + c] = aT.x[k];
     }
     __builtin_amdgcn_wave_barrier();   // the group is within one wave: LDS order is program order
     float *gr = sink.grel + (int64_t)rp * D, *gh = sink.gent + (int64_t)hp * D, *gt = sink.gent + (int64_t)tp * D;
@@ -517,15 +538,15 @@ __global__ __launch_bounds__(NT) void k_step_csr(StepParams P, GlobalSink sink, 
     for (int k = 0; k < KCH * VEC; ++k) {
         const int c = k * G + lane;
         if (c < D) {
-            atomicAdd(gr + c, tb[c]);
-            atomicAdd(gh + c, tb[RW + c]);
-            atomicAdd(gt + c, tb[2 * RW + c]);
+            if (dr < 0) atomicAdd(gr + c, tb[c]);
+            if (dh < 0) atomicAdd(gh + c, tb[RW + c]);
+            if (dt < 0) atomicAdd(gt + c, tb[2 * RW + c]);
         }
     }
     if (lane == 0) {
-        sink.frel[rp] = 1;
-        sink.fent[hp] = 1;
-        sink.fent[tp] = 1;
+        if (dr < 0) sink.frel[rp] = 1;
+        if (dh < 0) sink.fent[hp] = 1;
+        if (dt < 0) sink.fent[tp] = 1;
     }
 }
 
@@ -572,8 +593,8 @@ constexpr int csr_nch(int kch, int s) { return kch >= 4 && s == 1 ? 1 : kCsrNch;
 
 // TransE on the counting-sort path with float4 rows takes k_step_csr (the contribution rows always count
 // towards the offsets' 31 bits)
-static bool csr_fast_path(const StepParams &P) {
-    return P.model == 0 && P.dim % 4 == 0 && offsets_fit31(P, P.batch_size * P.neg);
+bool csr_fast_path(const StepParams &P) {
+    return P.model == 0 && P.dim % 4 == 0 && offsets_fit31(P, csr_con_rows(P.batch_size, P.neg));
 }
 
 // whether launch_step can take this (P, neg) on the in-kernel-sampled path: k_step_csr has no LDS

@@ -24,6 +24,10 @@ struct GraphKey {
     }
 };
 
+// uses of a table row by one step's positives that get a stored contribution row (the rest keep the float atomics):
+// measured on the fb15k237-shaped graph at batch 2000
+static const int32_t kDefaultEntCap = 8, kDefaultRelCap = 32;
+
 struct pt_trainer {
     pt::StepParams P{};
     pt::StepWorkspace W{};
@@ -43,6 +47,12 @@ struct pt_trainer {
     std::map<GraphKey, hipGraphExec_t> graphs;
     int path_override = -1;                             // pt_trainer_set_sampling: PT_PATH_* or -1 (automatic)
     int64_t parts_override = 0;                         // split-sampler workgroups per call (0: automatic)
+    // stored positive rows (pt_trainer_set_positive_caps): the caps asked for (-1: the library's choice) and whether
+    // the carved (bs, neg) takes the stored path at all (k_step_csr + k_apply_buf, k_pos_slots' plan fits LDS)
+    int32_t ent_cap_set = -1, rel_cap_set = -1;
+    bool pos_stored = false;
+    int32_t ent_cap() const { return !pos_stored ? 0 : ent_cap_set < 0 ? kDefaultEntCap : ent_cap_set; }
+    int32_t rel_cap() const { return !pos_stored ? 0 : rel_cap_set < 0 ? kDefaultRelCap : rel_cap_set; }
     // reference-order (deterministic) mode: ordered.hip's step on k_sample batches (pt_trainer_set_deterministic)
     bool ordered = false;
     void *ord_block = nullptr;
@@ -192,15 +202,15 @@ static int ensure_csr(pt_trainer *t, int64_t bs, int64_t neg) {
     if (t->csr_block && t->csr_bs == bs && t->csr_neg == neg) return PT_OK;
     // ---- sizes: per call the positives, slot records, slot destinations, bucket counts and starts; the
     // chunk's tickets; one step's contribution rows
-    const int64_t E = t->P.ent_total, D = t->P.dim;
-    const int64_t cs = (E + 3) & ~int64_t(3), ss = (E + 4) & ~int64_t(3);
+    const int64_t E = t->P.ent_total, R = t->P.rel_total, D = t->P.dim;
+    const int64_t cs = (E + 3) & ~int64_t(3), ss = (E + 4) & ~int64_t(3), ps = (E + R + 4) & ~int64_t(3);
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t per_call = 16 * bs + 8 * bs * neg + 4 * cs + 4 * ss + 4 + 1024;
+    const size_t per_call = 32 * bs + 8 * bs * neg + 4 * cs + 4 * ss + 4 * ps + 4 + 1024;
     const int64_t chunk = std::min<int64_t>(kCsrChunk, (int64_t)std::max<size_t>(1, ((size_t)512 << 20) / per_call));
     const size_t a_pos = al(16 * bs * chunk), a_neg = al(4 * bs * neg * chunk), a_off = a_neg,
                  a_cnt = al(4 * cs * chunk), a_start = al(4 * ss * chunk), a_tick = al(4 * chunk + 4),
-                 a_con = al(4 * bs * neg * D);
-    const size_t need = a_pos + a_neg + a_off + a_cnt + a_start + a_tick + a_con;
+                 a_con = al(4 * pt::csr_con_rows(bs, neg) * D), a_pdst = a_pos, a_pstart = al(4 * ps * chunk);
+    const size_t need = a_pos + a_neg + a_off + a_cnt + a_start + a_tick + a_con + a_pdst + a_pstart;
     // ---- (re)allocation
     PT_HIP(hipDeviceSynchronize());   // queued work may still use the old carving
     t->drop_graphs();
@@ -220,9 +230,15 @@ static int ensure_csr(pt_trainer *t, int64_t bs, int64_t neg) {
     t->csr.cnt = (int32_t *)b; b += a_cnt;
     t->csr.start = (int32_t *)b; b += a_start;
     t->csr.tick = (int32_t *)b; b += a_tick;
-    t->csr.contrib = (float *)b;
+    t->csr.contrib = (float *)b; b += a_con;
+    t->csr.pdst = (int4 *)b; b += a_pdst;
+    t->csr.pstart = (int32_t *)b;
     t->csr.cnt_stride = cs;
     t->csr.start_stride = ss;
+    t->csr.pstart_stride = ps;
+    // no positive row stored until k_pos_slots says so: every destination -1, every bucket empty
+    PT_HIP(hipMemset(t->csr.pdst, 0xff, a_pdst));
+    PT_HIP(hipMemsetD32((hipDeviceptr_t)t->csr.pstart, (int)(bs * neg), (size_t)(ps * chunk)));
     t->csr_bs = bs;
     t->csr_neg = neg;
     t->csr_chunk = chunk;
@@ -230,6 +246,11 @@ static int ensure_csr(pt_trainer *t, int64_t bs, int64_t neg) {
     // plans fit (sets the kernels' LDS attributes here, outside any stream capture)
     t->csr_fused = pt::sample_sort_prepare(bs, neg, E, ss);
     t->csr_part = pt::sample_part_prepare(bs, neg, E, std::min<int64_t>(bs, kPartTarget));
+    // the stored path is on only where both k_step_csr and k_apply_buf run (decided here, once per carving)
+    pt::StepParams Q = t->P;
+    Q.batch_size = bs;
+    Q.neg = neg;
+    t->pos_stored = pt::csr_fast_path(Q) && pt::pos_slots_prepare(bs, neg, E, R);
     return PT_OK;
 }
 
@@ -296,6 +317,10 @@ static int enqueue_sample_chunk(pt_trainer *t, pt_sampler *s, pt::CsrWork &w, in
         PT_TIMED(0, pt::launch_sample_csr(dg, s->d_states, s->threads, bs, neg, (int)bern, (int)filter, calls, w, st));
         PT_TIMED(1, pt::launch_scan_counts(w, t->P.ent_total, calls, s->d_states, s->threads, bs, dpp, st));
     }
+    // the positives' stored rows (caps 0 / 0: pdst and pstart stay as ensure_csr left them, all atomic)
+    if (t->ent_cap() > 0 || t->rel_cap() > 0)
+        PT_TIMED(0, pt::launch_pos_slots(w, bs, neg, t->P.ent_total, t->P.rel_total, t->ent_cap(), t->rel_cap(), calls,
+                                         st));
     return PT_OK;
 }
 
@@ -525,6 +550,23 @@ extern "C" int pt_trainer_set_sampling(pt_trainer *t, int32_t path, int64_t part
     t->path_override = path;
     t->parts_override = parts;
     t->drop_graphs();   // captured epochs hold the previous choice
+    return PT_OK;
+}
+
+extern "C" int pt_trainer_set_positive_caps(pt_trainer *t, int32_t ent_cap, int32_t rel_cap) {
+    PT_CHECK(t, PT_EINVAL, "null trainer");
+    PT_CHECK(ent_cap >= -1 && rel_cap >= -1, PT_EINVAL, "positive caps must be >= 0, or -1 for the library's choice");
+    PT_HIP(hipDeviceSynchronize());   // queued work may still read the previous slots
+    t->ent_cap_set = ent_cap;
+    t->rel_cap_set = rel_cap;
+    t->drop_graphs();   // captured epochs hold the previous caps
+    t->csr_bs = 0;      // re-carve: pdst / pstart return to "nothing stored"
+    return PT_OK;
+}
+extern "C" int pt_trainer_positive_caps(const pt_trainer *t, int32_t *ent_cap, int32_t *rel_cap) {
+    PT_CHECK(t && ent_cap && rel_cap, PT_EINVAL, "pt_trainer_positive_caps: null argument");
+    *ent_cap = t->ent_cap_set < 0 ? kDefaultEntCap : t->ent_cap_set;
+    *rel_cap = t->rel_cap_set < 0 ? kDefaultRelCap : t->rel_cap_set;
     return PT_OK;
 }
 
@@ -809,6 +851,28 @@ extern "C" int pt_trainer_sample_csr(pt_trainer *t, pt_sampler *s, int64_t bs, i
         h_pos[3 * i + 1] = pos[i].y;
         h_pos[3 * i + 2] = pos[i].z;
     }
+    return PT_OK;
+}
+
+extern "C" int pt_trainer_positive_slots(pt_trainer *t, int64_t calls, int32_t *h_pdst, int32_t *h_pstart,
+                                         int32_t *stored, void *stream) {
+    PT_CHECK(t && h_pdst && h_pstart && stored, PT_EINVAL, "pt_trainer_positive_slots: null argument");
+    PT_CHECK(t->csr_block && calls > 0 && calls <= t->csr_chunk, PT_ESTATE,
+             "pt_trainer_positive_slots: no sampled chunk of that many calls (pt_trainer_sample_csr first)");
+    hipStream_t st = (hipStream_t)stream;
+    const pt::CsrWork &w = t->csr;
+    const int64_t bs = t->csr_bs, n = t->P.ent_total + t->P.rel_total + 1;
+    std::vector<int4> d((size_t)(calls * bs));
+    PT_HIP(hipMemcpyAsync(d.data(), w.pdst, sizeof(int4) * d.size(), hipMemcpyDeviceToHost, st));
+    PT_HIP(hipMemcpy2DAsync(h_pstart, 4 * (size_t)n, w.pstart, 4 * (size_t)w.pstart_stride, 4 * (size_t)n, (size_t)calls,
+                            hipMemcpyDeviceToHost, st));
+    PT_HIP(hipStreamSynchronize(st));
+    for (size_t i = 0; i < d.size(); ++i) {
+        h_pdst[3 * i] = d[i].x;
+        h_pdst[3 * i + 1] = d[i].y;
+        h_pdst[3 * i + 2] = d[i].z;
+    }
+    *stored = t->pos_stored ? 1 : 0;
     return PT_OK;
 }
 

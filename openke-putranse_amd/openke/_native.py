@@ -119,6 +119,9 @@ SIGNATURES = {
     "pt_trainer_last_path": (ctypes.c_int, [c_vp]),
     "pt_trainer_set_deterministic": (ctypes.c_int, [c_vp, c_i32]),
     "pt_trainer_set_sampling": (ctypes.c_int, [c_vp, c_i32, c_i64]),
+    "pt_trainer_set_positive_caps": (ctypes.c_int, [c_vp, c_i32, c_i32]),
+    "pt_trainer_positive_caps": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
+    "pt_trainer_positive_slots": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, ctypes.POINTER(c_i32), c_vp]),
     "pt_trainer_set_sample_split": (ctypes.c_int, [c_vp, c_i64]),   # shim of a removed mode (putranse.h)
     "pt_trainer_set_step_apply": (ctypes.c_int, [c_vp, c_i32]),   # shim of a removed mode (putranse.h)
     "pt_universe_dim_supported": (ctypes.c_int, [c_i64, c_i32]),

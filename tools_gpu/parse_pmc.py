@@ -54,7 +54,7 @@ if len(sys.argv) > 2 and sys.argv[2].endswith("_uni.json"):   # universe workloa
 if len(sys.argv) > 2:
     sampled = float(sys.argv[3]) if len(sys.argv) > 3 else None
     # (per chunk of sampled steps)
-    samplers = ("k_sample_csr", "k_scan_counts", "k_sample_sort", "k_advance", "k_sample_part")
+    samplers = ("k_sample_csr", "k_scan_counts", "k_sample_sort", "k_advance", "k_sample_part", "k_pos_slots")
     per_step = ("k_step_csr", "k_step_sampled", "k_apply")
     def kb(d):
         return 2.0 * sum(d.get("FETCH_SIZE", [])) + sum(d.get("WRITE_SIZE", []))
