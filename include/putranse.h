@@ -95,11 +95,22 @@ int pt_sampler_sample_ex(pt_sampler *s, int64_t bs, int64_t neg, int64_t neg_rel
  * weights, score_margin_flag = 0; PT_LOSS_MARGIN, a model margin, a sampler passed to pt_trainer_step, pt_trainer_run,
  * pt_trainer_run_timed, the reference-order mode and every universe entry point refuse it (PT_ENOTSUP). The model's
  * regularisers come through pt_trainer_set_regul. neg_ent is limited as for the weighted TransE step at the same dim. */
-enum { PT_TRANSE = 0, PT_TRANSH = 1, PT_TRANSD = 2, PT_ROTATE = 3, PT_DISTMULT = 4 };
+/* PT_COMPLEX (ComplEx.py): one model through pt_trainer_step on external batches and pt_score / pt_score_queries /
+ * pt_score_rows, which return -s with s = sum_j h_re t_re r_re + h_im t_im r_re + h_re t_im r_im - h_im t_re r_im
+ * (what predict returns: lower is better). Four tables [rows][dim]: ent and rel carry ent_re and rel_re, ent_transfer
+ * and rel_transfer carry ent_im and rel_im (null: PT_EINVAL); the im tables' Adagrad sums come in ent_transfer_acc /
+ * rel_transfer_acc, their Adam moments in pt_adam_state's *_transfer_m / *_transfer_v. dim is the row length of one
+ * table, under PT_TRANSE's dim rule. Nothing is normalised; p_norm, norm_flag, normv and phase_div are not read. The
+ * score goes to the loss as it is: PT_LOSS_SIGMOID only, with or without the adversarial weights, score_margin_flag =
+ * 0; PT_LOSS_MARGIN, a model margin, a sampler passed to pt_trainer_step, pt_trainer_run, pt_trainer_run_timed, the
+ * reference-order mode and every universe entry point refuse it (PT_ENOTSUP). regul_rate comes through
+ * pt_trainer_set_regul (batch_mode 0 only, no l3). SGD, Adagrad and Adam; the optimizer pass runs twice, over the re
+ * and over the im tables. neg_ent is limited as for PT_DISTMULT at the same dim. */
+enum { PT_TRANSE = 0, PT_TRANSH = 1, PT_TRANSD = 2, PT_ROTATE = 3, PT_DISTMULT = 4, PT_COMPLEX = 5 };
 enum { PT_SGD = 0, PT_ADAGRAD = 1, PT_ADAM = 2 };
 
 typedef struct {
-    int32_t model;        /* PT_TRANSE | PT_TRANSH | PT_TRANSD | PT_ROTATE | PT_DISTMULT */
+    int32_t model;        /* PT_TRANSE | PT_TRANSH | PT_TRANSD | PT_ROTATE | PT_DISTMULT | PT_COMPLEX */
     int32_t p_norm;       /* 1 or 2  (TransE.py:46-60) */
     int32_t norm_flag;    /* F.normalize of h, r, t before scoring */
     int32_t opt;          /* PT_SGD | PT_ADAGRAD (Trainer.py:62-88; eps 1e-10, lr_decay 0) | PT_ADAM (state:
@@ -109,8 +120,9 @@ typedef struct {
     int64_t ent_total, rel_total, dim;
     float *ent, *rel, *normv;              /* device tables [rows][dim], row-major fp32 */
     float *ent_acc, *rel_acc, *norm_acc;   /* Adagrad state_sum (NULL for SGD) */
-    /* PT_TRANSD only (NULL otherwise): ent_transfer [ent_total][dim], rel_transfer [rel_total][dim] and their
-     * Adagrad state_sum. Appended: a caller that zero-initialises the struct and fills the fields above is unchanged. */
+    /* PT_TRANSD and PT_COMPLEX (its im tables) only (NULL otherwise): ent_transfer [ent_total][dim], rel_transfer
+     * [rel_total][dim] and their Adagrad state_sum. Appended: a caller that zero-initialises the struct and fills the
+     * fields above is unchanged. */
     float *ent_transfer, *rel_transfer, *ent_transfer_acc, *rel_transfer_acc;
     /* PT_ROTATE only (appended, ignored otherwise): the phase divisor q = float32(rel_embedding_range / pi); the phase
      * of a relation element is r / q. Finite and > 0, else PT_EINVAL. */
@@ -196,7 +208,7 @@ typedef struct {
     float *ent_v, *rel_v, *norm_v;   /* exp_avg_sq */
     double beta1, beta2, eps;        /* doubles: 1 - beta is formed in double, as torch forms it */
     int64_t step;
-    /* PT_TRANSD only (NULL otherwise): the moments of ent_transfer and rel_transfer */
+    /* PT_TRANSD and PT_COMPLEX only (NULL otherwise): the moments of ent_transfer and rel_transfer (ent_im, rel_im) */
     float *ent_transfer_m, *rel_transfer_m, *ent_transfer_v, *rel_transfer_v;
 } pt_adam_state;
 int pt_trainer_set_adam(pt_trainer *t, const pt_adam_state *state);
@@ -207,8 +219,10 @@ int pt_trainer_set_adam(pt_trainer *t, const pt_adam_state *state);
  * positive; pt_trainer_step still takes the expanded arrays). It is computed inside the step kernel and works with
  * every optimizer. l3_regul_rate: DistMult.l3_regularization, l3 * (||ent||_3^3 + ||rel||_3^3) over the whole tables;
  * dense, so it rides the PT_ADAM pass only: a step with l3_regul_rate != 0 under PT_SGD / PT_ADAGRAD returns
- * PT_ENOTSUP. Both join the step's loss value. A nonzero rate on any other model: PT_ENOTSUP; a negative or
- * non-finite rate, batch_mode outside 0..2: PT_EINVAL. */
+ * PT_ENOTSUP. Both join the step's loss value. PT_COMPLEX takes regul_rate too (ComplEx.regularization: the mean of
+ * the six means of squares over every slot's re and im rows) with batch_mode 0 only - ComplEx.forward ignores the batch
+ * mode - and defines no l3 regulariser: another batch_mode or a nonzero l3_regul_rate is PT_ENOTSUP. A nonzero rate on
+ * any other model: PT_ENOTSUP; a negative or non-finite rate, batch_mode outside 0..2: PT_EINVAL. */
 typedef struct {
     float regul_rate, l3_regul_rate;
     int32_t batch_mode;   /* 0 normal, 1 head_batch, 2 tail_batch */
@@ -217,8 +231,9 @@ int pt_trainer_set_regul(pt_trainer *t, const pt_regul_desc *r);
 int64_t pt_trainer_adam_step(const pt_trainer *t);
 /* Measurement hook of the external-batch step (tools/bench_adv.py): `steps` steps on ONE device batch (layout of
  * pt_trainer_step), launched one by one with events around both launches of every step. ms2[0] = mean duration of
- * the step kernel (k_step / k_step_adv / k_step_transd / k_step_rotate / k_step_distmult), ms2[1] = of the apply
- * kernel (k_apply / k_apply_adam; both launches of it for PT_TRANSD; with l3_regul_rate its loss launch too). The
+ * the step kernel (k_step / k_step_adv / k_step_transd / k_step_rotate / k_step_distmult / k_step_complex), ms2[1] = of
+ * the apply kernel (k_apply / k_apply_adam; both launches of it for PT_TRANSD and PT_COMPLEX; with l3_regul_rate its
+ * loss launch too). The
  * steps train:
  * tables, optimizer state and the Adam step count advance, *d_loss accumulates. Synchronizes the stream. */
 int pt_trainer_steps_timed(pt_trainer *t, int64_t bs, int64_t neg, const int64_t *d_batch_h, const int64_t *d_batch_t,
@@ -360,7 +375,7 @@ int pt_universe_dim_supported(int64_t dim, int32_t model);
  * 1..512; else 0 (those calls then fail with PT_ENOTSUP). No device call. It answers for these three models, as it
  * did before PT_ROTATE existed, and 0 for every other model id, 3 (PT_ROTATE) included: callers use 3 as an id no
  * model has. PT_ROTATE's pt_model_desc.dim (its relation row's) follows PT_TRANSE's rule: ask with PT_TRANSE. The
- * same holds for 4 (PT_DISTMULT): 0 here, PT_TRANSE's rule in pt_trainer_create / pt_score*. */
+ * same holds for 4 (PT_DISTMULT) and 5 (PT_COMPLEX): 0 here, PT_TRANSE's rule in pt_trainer_create / pt_score*. */
 int pt_model_dim_supported(int64_t dim, int32_t model);
 /* reference-order (deterministic) mode of a set (see pt_trainer_set_deterministic): one workgroup per
  * universe runs its steps with the ordered per-row sums; its workspace is allocated on first use */

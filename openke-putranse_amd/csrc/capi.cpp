@@ -35,24 +35,29 @@ extern "C" int pt_version(void) { return 1; }
 int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
     PT_CHECK(m, PT_EINVAL, "null model descriptor");
     PT_CHECK(m->model == PT_TRANSE || m->model == PT_TRANSH || m->model == PT_TRANSD || m->model == PT_ROTATE ||
-                 m->model == PT_DISTMULT,
-             PT_EINVAL, "model must be PT_TRANSE, PT_TRANSH, PT_TRANSD, PT_ROTATE or PT_DISTMULT");
-    PT_CHECK(m->model == PT_DISTMULT || m->p_norm == 1 || m->p_norm == 2, PT_ENOTSUP, "p_norm must be 1 or 2");
+                 m->model == PT_DISTMULT || m->model == PT_COMPLEX,
+             PT_EINVAL, "model must be PT_TRANSE, PT_TRANSH, PT_TRANSD, PT_ROTATE, PT_DISTMULT or PT_COMPLEX");
+    PT_CHECK(m->model == PT_DISTMULT || m->model == PT_COMPLEX || m->p_norm == 1 || m->p_norm == 2, PT_ENOTSUP,
+             "p_norm must be 1 or 2");
     PT_CHECK(m->opt == PT_SGD || m->opt == PT_ADAGRAD || m->opt == PT_ADAM, PT_EINVAL,
              "opt must be PT_SGD, PT_ADAGRAD or PT_ADAM");
     PT_CHECK(m->model != PT_TRANSD || pt::model_dim_supported(m->dim, m->model), PT_ENOTSUP,
              "embedding dim " + std::to_string(m->dim) + " not supported: TransD takes dims 1..512");
     PT_CHECK(pt::model_dim_supported(m->dim, m->model), PT_ENOTSUP,
              "embedding dim " + std::to_string(m->dim) +
-                 " not supported: TransE, TransH, RotatE and DistMult take dims 1..512 and multiples of 4 from 516 to 1024");
+                 " not supported: TransE, TransH, RotatE, DistMult and ComplEx take dims 1..512 and multiples of 4 from 516 "
+                 "to 1024");
     PT_CHECK(m->model != PT_ROTATE || (std::isfinite(m->phase_div) && m->phase_div > 0.f), PT_EINVAL,
              "PT_ROTATE needs a finite phase divisor > 0 (pt_model_desc.phase_div = rel_embedding_range / pi)");
     PT_CHECK(m->ent && m->rel && m->ent_total > 0 && m->rel_total > 0, PT_EINVAL, "missing tables");
     PT_CHECK(m->model != PT_TRANSH || m->normv, PT_EINVAL, "TransH needs norm_vector");
     PT_CHECK(m->model != PT_TRANSD || (m->ent_transfer && m->rel_transfer), PT_EINVAL,
              "TransD needs ent_transfer and rel_transfer");
+    PT_CHECK(m->model != PT_COMPLEX || (m->ent_transfer && m->rel_transfer), PT_EINVAL,
+             "PT_COMPLEX needs its im tables in ent_transfer and rel_transfer (ent and rel carry the re tables)");
     PT_CHECK(m->opt != PT_ADAGRAD || (m->ent_acc && m->rel_acc && (m->model != PT_TRANSH || m->norm_acc) &&
-                                      (m->model != PT_TRANSD || (m->ent_transfer_acc && m->rel_transfer_acc))),
+                                      ((m->model != PT_TRANSD && m->model != PT_COMPLEX) ||
+                                       (m->ent_transfer_acc && m->rel_transfer_acc))),
              PT_EINVAL, "Adagrad needs state_sum buffers");
     P.model = m->model;
     P.p_norm = m->p_norm;
@@ -66,12 +71,13 @@ int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
     P.ent = m->ent; P.rel = m->rel; P.normv = m->normv;
     P.ent_acc = m->ent_acc; P.rel_acc = m->rel_acc; P.norm_acc = m->norm_acc;
     if (m->model == PT_ROTATE) P.phase_div = m->phase_div;
-    if (m->model == PT_DISTMULT) {   // (p_norm, norm_flag and normv are not read: nothing of it is normalised)
+    // (p_norm, norm_flag and normv are not read: nothing of either model is normalised)
+    if (m->model == PT_DISTMULT || m->model == PT_COMPLEX) {
         P.p_norm = 1;
         P.norm_flag = 0;
         P.normv = nullptr;
     }
-    if (m->model == PT_TRANSD) {
+    if (m->model == PT_TRANSD || m->model == PT_COMPLEX) {   // (PT_COMPLEX: the im tables and their Adagrad sums)
         P.ent_t = m->ent_transfer; P.rel_t = m->rel_transfer;
         P.ent_t_acc = m->ent_transfer_acc; P.rel_t_acc = m->rel_transfer_acc;
     }
@@ -80,7 +86,7 @@ int pt::desc_to_params(const pt_model_desc *m, pt::StepParams &P) {
 
 // (answers for the three translational models, as it always has: PT_ROTATE's dims are PT_TRANSE's, putranse.h)
 extern "C" int pt_model_dim_supported(int64_t dim, int32_t model) {
-    return model != PT_ROTATE && model != PT_DISTMULT && pt::model_dim_supported(dim, model) ? 1 : 0;
+    return model >= PT_TRANSE && model <= PT_TRANSD && pt::model_dim_supported(dim, model) ? 1 : 0;
 }
 
 // ======================================================================== graphs =================
@@ -350,6 +356,7 @@ extern "C" int pt_lp_min_scores(const pt_lp_universe *us, int64_t n_universes, i
     PT_CHECK(model != PT_ROTATE, PT_ENOTSUP, "pt_lp_min_scores: PT_ROTATE trains and ranks one model, not universes");
     PT_CHECK(model != PT_DISTMULT, PT_ENOTSUP,
              "pt_lp_min_scores: PT_DISTMULT trains and ranks one model, not universes");
+    PT_CHECK(model != PT_COMPLEX, PT_ENOTSUP, "pt_lp_min_scores: PT_COMPLEX trains and ranks one model, not universes");
     PT_CHECK((us && pairs && d_key_rows) || n_pairs == 0, PT_EINVAL, "pt_lp_min_scores: null argument");
     if (n_pairs == 0) return PT_OK;
     hipStream_t st = (hipStream_t)stream;

@@ -18,8 +18,8 @@ struct StepParams {
     int64_t batch_size, neg;
     float inv_count;   // 1 / (batch_size * neg)
     int loss_assign = 0;   // the apply pass stores the step's loss (=) instead of adding it (+=)
-    // TransD (model 2): ent_transfer / rel_transfer and their Adagrad state (appended: the fields above keep their
-    // places in the argument blocks of the TransE / TransH kernels)
+    // TransD (model 2): ent_transfer / rel_transfer and their Adagrad state; ComplEx (model 5): ent_im / rel_im and
+    // theirs (appended: the fields above keep their places in the argument blocks of the TransE / TransH kernels)
     float *ent_t = nullptr, *rel_t = nullptr;
     float *ent_t_acc = nullptr, *rel_t_acc = nullptr;
     // RotatE (model 3): an entity row holds 2 * dim floats (re | im), a relation row dim phases; phase = r / phase_div
@@ -109,7 +109,7 @@ constexpr Shape pick_shape(int64_t D, bool vec4 = true) {
 }
 
 // instantiated (G, VEC, KCH) row shapes: float4 rows up to dim 1,024 (KCH 3 and 4: dims 516..1,024, TransE and TransH
-// RotatE and DistMult single models only; model_dim_supported is the rule), one-float rows up to dim 512
+// RotatE, DistMult and ComplEx single models only; model_dim_supported is the rule), one-float rows up to dim 512
 #define PT_SHAPES(X)                                                                                  \
     X(2, 4, 1) X(4, 4, 1) X(8, 4, 1) X(16, 4, 1) X(32, 4, 1) X(64, 4, 1) X(64, 4, 2) X(64, 4, 3)     \
     X(64, 4, 4)                                                                                       \
@@ -142,8 +142,9 @@ constexpr bool for_value(int v, F &&f) {
 
 // ---- kernels.hip: the dim rule and the score kernels
 // The one dim rule of the single-model path (pt_model_dim_supported answers it for models 0-2): dims 1..512 for every model (both row layouts
-// exist), dims 516..1,024 in multiples of 4 (float4 rows only) for TransE (0), TransH (1), RotatE (3) and DistMult
-// (4); nothing else. RotatE's dim is its relation row's: an entity row is two such rows, re | im
+// exist), dims 516..1,024 in multiples of 4 (float4 rows only) for TransE (0), TransH (1), RotatE (3), DistMult (4)
+// and ComplEx (5); nothing else. RotatE's dim is its relation row's: an entity row is two such rows, re | im; ComplEx's
+// is the row length of one of its four tables
 bool model_dim_supported(int64_t dim, int model);
 // dims at which both row layouts exist (1..512): what the one-float kernels (k_step_sampled, k_lp_scan_t's tile) take
 bool narrow_dim_supported(int64_t dim);
@@ -220,7 +221,7 @@ inline void loss_affine(const LossParams &L, const StepParams &P, float *scale, 
 }
 // dense Adam (adam.hip; pt_adam_state): m / v per table, the step's bias corrections computed on the host in double
 struct AdamParams {
-    // tables 0-2: ent, rel, norm_vector; 3-4: TransD's ent_transfer, rel_transfer
+    // tables 0-2: ent, rel, norm_vector; 3-4: TransD's ent_transfer, rel_transfer (ComplEx's ent_im, rel_im)
     float *m[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     double beta1 = 0.9, beta2 = 0.999, eps = 1e-8;   // (1 - beta in double: 1.0f - 0.999f is 1.3e-5 off 0.001)
     float step_size = 0.f;   // lr / (1 - beta1^t)
@@ -248,8 +249,9 @@ hipError_t launch_score_transd(const StepParams &P, int mode, const int64_t *h, 
 hipError_t launch_score_queries_transd(const StepParams &P, int side, const int64_t *qh, const int64_t *qt,
                                        const int64_t *qr, int64_t nq, int64_t E, float *out, hipStream_t st,
                                        int global_order);
-// the (ent_transfer, rel_transfer) pair of a TransD step seen as the (ent, rel) pair of a second optimizer pass: no
-// Jacobian (the step kernel finished both gradients), no loss partials (the first pass reduced them)
+// the (ent_transfer, rel_transfer) pair of a TransD step - or the (ent_im, rel_im) pair of a ComplEx step, which rides
+// the same fields - seen as the (ent, rel) pair of a second optimizer pass: no Jacobian (the step kernel finished both
+// gradients), no loss partials (the first pass reduced them)
 inline void transd_transfer_pass(const StepParams &P, const StepWorkspace &W, StepParams *P2, StepWorkspace *W2) {
     *P2 = P;
     P2->ent = P.ent_t; P2->rel = P.rel_t;
@@ -300,6 +302,23 @@ hipError_t launch_score_distmult(const StepParams &P, int mode, const int64_t *h
 hipError_t launch_score_queries_distmult(const StepParams &P, int side, const int64_t *qh, const int64_t *qt,
                                          const int64_t *qr, int64_t nq, int64_t E, float *out, hipStream_t st,
                                          int global_order);
+
+// ComplEx (complex.hip, model 5): four tables [rows][dim]; ent / rel carry the re halves, ent_t / rel_t the im halves
+// (their Adagrad sums in ent_t_acc / rel_t_acc, their gradient rows and flags in gentt / grelt / fentt / frelt), nothing
+// normalised. The external-batch step under SigmoidLoss with or without the adversarial weights (the score goes to the
+// loss as it is: no model margin), with ComplEx.regularization folded in (RegulParams::regul; mode 0 only, no l3); the
+// scores -s behind pt_score*; launch_score / launch_score_queries route model 5 to the latter two. The optimizer pass
+// runs twice: (ent_re, rel_re), then transd_transfer_pass's view of (ent_im, rel_im)
+int64_t step_complex_max_neg(int64_t dim);
+hipError_t launch_step_complex(const StepParams &P, const LossParams &L, const RegulParams &Rg, const int64_t *bh,
+                               const int64_t *bt, const int64_t *br, const StepWorkspace &W, hipStream_t st);
+hipError_t launch_score_complex(const StepParams &P, int mode, const int64_t *h, const int64_t *t, const int64_t *r,
+                                int64_t n, float *out, hipStream_t st);
+// queries a lane group of k_score_queries_complex serves per pass over the entity rows at this dim
+int complex_queries_per_group(int64_t dim);
+hipError_t launch_score_queries_complex(const StepParams &P, int side, const int64_t *qh, const int64_t *qt,
+                                        const int64_t *qr, int64_t nq, int64_t E, float *out, hipStream_t st,
+                                        int global_order);
 
 hipError_t launch_torch_init(const pt_torch_init_job *d_jobs, int64_t n, hipStream_t st);
 hipError_t launch_rank_rows(const float *rows, int64_t E, const int64_t *row_of, const int64_t *truth,

@@ -128,24 +128,25 @@ constexpr bool wide_dispatches(int64_t dim) {
     return dim > 512 && dim <= 1024 && dim % 4 == 0 && shape_listed(pick_shape(dim));
 }
 constexpr bool dim_dispatches(int64_t dim, int model) {
-    return narrow_dispatches(dim) || ((model == 0 || model == 1 || model == 3 || model == 4) && wide_dispatches(dim));
+    return narrow_dispatches(dim) || (model != 2 && model >= 0 && model <= 5 && wide_dispatches(dim));
 }
 constexpr bool dim_rule_holds() {
     for (int64_t dim = 1; dim <= 512; ++dim)
-        for (int model = 0; model < 5; ++model)
+        for (int model = 0; model < 6; ++model)
             if (!dim_dispatches(dim, model)) return false;
     for (int64_t dim = 513; dim <= 1100; ++dim)
-        for (int model = 0; model < 5; ++model)
+        for (int model = 0; model < 6; ++model)
             if (dim_dispatches(dim, model) != (model != 2 && dim <= 1024 && dim % 4 == 0)) return false;
     return !dim_dispatches(0, 0) && !dim_dispatches(513, 0) && !dim_dispatches(514, 0) && !dim_dispatches(1028, 0) &&
            !dim_dispatches(516, 2) && dim_dispatches(1024, 3) && !dim_dispatches(1028, 3) &&
-           dim_dispatches(1024, 4) && !dim_dispatches(1028, 4);
+           dim_dispatches(1024, 4) && !dim_dispatches(1028, 4) && dim_dispatches(1024, 5) &&
+           !dim_dispatches(1028, 5);
 }
 static_assert(dim_rule_holds(),
               "PT_SHAPES must cover dims 1..512 under both layouts and dims 516..1024 (multiples of 4) as float4 rows "
-              "for TransE / TransH / RotatE / DistMult; 513, 514, 1028 and TransD above 512 must not dispatch");
+              "for TransE / TransH / RotatE / DistMult / ComplEx; 513, 514, 1028 and TransD above 512 must not dispatch");
 
-bool model_dim_supported(int64_t dim, int model) { return model >= 0 && model <= 4 && dim_dispatches(dim, model); }
+bool model_dim_supported(int64_t dim, int model) { return model >= 0 && model <= 5 && dim_dispatches(dim, model); }
 bool narrow_dim_supported(int64_t dim) { return narrow_dispatches(dim); }
 
 hipError_t launch_score(const StepParams &P, int mode, const int64_t *h, const int64_t *t, const int64_t *r, int64_t n,
@@ -154,6 +155,7 @@ hipError_t launch_score(const StepParams &P, int mode, const int64_t *h, const i
     if (P.model == 2) return launch_score_transd(P, mode, h, t, r, n, out, st);
     if (P.model == 3) return launch_score_rotate(P, mode, h, t, r, n, out, st);
     if (P.model == 4) return launch_score_distmult(P, mode, h, t, r, n, out, st);
+    if (P.model == 5) return launch_score_complex(P, mode, h, t, r, n, out, st);
     const Shape s = pick_shape(P.dim);
     const int64_t gpb = 256 / s.G;
     const dim3 grid((unsigned)((n + gpb - 1) / gpb)), block(256);
@@ -175,6 +177,7 @@ hipError_t launch_score_queries(const StepParams &P, int side, const int64_t *qh
     if (P.model == 2) return launch_score_queries_transd(P, side, qh, qt, qr, nq, E, out, st, global_order);
     if (P.model == 3) return launch_score_queries_rotate(P, side, qh, qt, qr, nq, E, out, st, global_order);
     if (P.model == 4) return launch_score_queries_distmult(P, side, qh, qt, qr, nq, E, out, st, global_order);
+    if (P.model == 5) return launch_score_queries_complex(P, side, qh, qt, qr, nq, E, out, st, global_order);
     const Shape s = pick_shape(P.dim);
     const int64_t gpb = 256 / s.G;
     int64_t bx = (E + gpb - 1) / gpb;

@@ -71,7 +71,7 @@ struct pt_trainer {
     // anything the in-kernel-sampled, captured and reference-order paths do not compute
     bool extended() const {
         return !loss.plain() || P.opt == PT_ADAM || P.model == PT_TRANSD || P.model == PT_ROTATE ||
-               P.model == PT_DISTMULT;
+               P.model == PT_DISTMULT || P.model == PT_COMPLEX;
     }
     void drop_graphs() {
         for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
@@ -131,8 +131,8 @@ extern "C" int pt_trainer_create(const pt_model_desc *m, pt_trainer **out) {
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t ge = al(4 * E * D), gr = al(4 * R * D), gn = m->model == PT_TRANSH ? al(4 * R * D) : 0;
     const size_t fe = al(4 * E), fr = al(4 * R), fn = m->model == PT_TRANSH ? al(4 * R) : 0;
-    // TransD: gradient rows and flags of ent_transfer / rel_transfer, shaped like ent / rel
-    const bool td = m->model == PT_TRANSD;
+    // TransD: gradient rows and flags of ent_transfer / rel_transfer, shaped like ent / rel (ComplEx: of its im tables)
+    const bool td = m->model == PT_TRANSD || m->model == PT_COMPLEX;
     const size_t total = ge + gr + gn + fe + fr + fn + (td ? ge + gr + fe + fr : 0);
     PT_HIP(hipMalloc(&t->ws_block, total));
     PT_HIP(hipMemset(t->ws_block, 0, total));
@@ -380,9 +380,19 @@ static int enqueue_external(pt_trainer *t, int64_t bs, int64_t neg, const int64_
     PT_CHECK(!adam || t->adam_set, PT_ESTATE, "PT_ADAM needs pt_trainer_set_adam before the first step");
     float scale = P.inv_count, cst = P.margin;   // loss = scale * sum(lpart) + cst
     if (ev) PT_HIP(hipEventRecord(ev[0], st));
-    const bool transd = P.model == PT_TRANSD;
+    const bool complex = P.model == PT_COMPLEX;
+    const bool transd = P.model == PT_TRANSD || complex;   // (two optimizer passes: transd_transfer_pass)
     const float l3 = P.model == PT_DISTMULT ? t->regul.l3 : 0.f;
-    if (P.model == PT_DISTMULT) {
+    if (complex) {
+        PT_CHECK(t->loss.kind == PT_LOSS_SIGMOID && !t->loss.mflag, PT_ENOTSUP,
+                 "PT_COMPLEX trains under PT_LOSS_SIGMOID on the raw score (pt_trainer_set_loss before the first "
+                 "step): PT_LOSS_MARGIN and a model margin are not implemented for it");
+        PT_CHECK(neg <= pt::step_complex_max_neg(P.dim), PT_ENOTSUP,
+                 "neg_ent " + std::to_string(neg) + " too large for the PT_COMPLEX step's LDS score buffer (max " +
+                     std::to_string(pt::step_complex_max_neg(P.dim)) + ")");
+        pt::loss_affine(t->loss, P, &scale, &cst);
+        PT_HIP(pt::launch_step_complex(P, t->loss, t->regul, bh, bt, br, t->W, st));
+    } else if (P.model == PT_DISTMULT) {
         PT_CHECK(t->loss.kind == PT_LOSS_SIGMOID && !t->loss.mflag, PT_ENOTSUP,
                  "PT_DISTMULT trains under PT_LOSS_SIGMOID on the raw score (pt_trainer_set_loss before the first "
                  "step): PT_LOSS_MARGIN and a model margin are not implemented for it");
@@ -405,7 +415,7 @@ static int enqueue_external(pt_trainer *t, int64_t bs, int64_t neg, const int64_
         pt::loss_affine(t->loss, P, &scale, &cst);
         PT_HIP(pt::launch_step_rotate(P, t->loss, bh, bt, br, t->W, st));
         P = pt::rotate_half_rows(P);   // the optimizer passes see the entity table as half rows
-    } else if (transd) {
+    } else if (P.model == PT_TRANSD) {
         PT_CHECK(t->loss.plain(), PT_ENOTSUP,
                  "SigmoidLoss, adversarial weights and a model margin train TransE only (TransD is not implemented)");
         PT_HIP(pt::launch_step_transd(P, bh, bt, br, t->W, st));
@@ -453,8 +463,8 @@ static int enqueue_external(pt_trainer *t, int64_t bs, int64_t neg, const int64_
 }
 
 static const char *kExtendedMsg =
-    "a non-default loss (pt_trainer_set_loss), PT_ADAM, PT_TRANSD, PT_ROTATE and PT_DISTMULT train external batches only: "
-    "in-kernel sampling, captured runs and the reference-order mode are not implemented for them";
+    "a non-default loss (pt_trainer_set_loss), PT_ADAM, PT_TRANSD, PT_ROTATE, PT_DISTMULT and PT_COMPLEX train external "
+    "batches only: in-kernel sampling, captured runs and the reference-order mode are not implemented for them";
 
 // per-positive loss partials for batches of up to `bs` positives (grown on demand, never during a
 // capture: callers prepare before enqueueing)
@@ -576,6 +586,7 @@ extern "C" int pt_trainer_set_deterministic(pt_trainer *t, int32_t on) {
     PT_CHECK(!on || t->P.model != PT_TRANSD, PT_ENOTSUP, "reference-order mode is not implemented for TransD");
     PT_CHECK(!on || t->P.model != PT_ROTATE, PT_ENOTSUP, "reference-order mode is not implemented for PT_ROTATE");
     PT_CHECK(!on || t->P.model != PT_DISTMULT, PT_ENOTSUP, "reference-order mode is not implemented for PT_DISTMULT");
+    PT_CHECK(!on || t->P.model != PT_COMPLEX, PT_ENOTSUP, "reference-order mode is not implemented for PT_COMPLEX");
     t->ordered = on != 0;
     return PT_OK;
 }
@@ -594,7 +605,12 @@ extern "C" int pt_trainer_set_loss(pt_trainer *t, const pt_loss_desc *l) {
     PT_CHECK(t->P.model != PT_DISTMULT || (L.kind == PT_LOSS_SIGMOID && !L.mflag), PT_ENOTSUP,
              "PT_DISTMULT trains under PT_LOSS_SIGMOID on the raw score: PT_LOSS_MARGIN and score_margin_flag != 0 are "
              "not implemented for it");
-    PT_CHECK(L.plain() || t->P.model == PT_TRANSE || t->P.model == PT_ROTATE || t->P.model == PT_DISTMULT, PT_ENOTSUP,
+    PT_CHECK(t->P.model != PT_COMPLEX || (L.kind == PT_LOSS_SIGMOID && !L.mflag), PT_ENOTSUP,
+             "PT_COMPLEX trains under PT_LOSS_SIGMOID on the raw score: PT_LOSS_MARGIN and score_margin_flag != 0 (a "
+             "model margin) are not implemented for it");
+    PT_CHECK(L.plain() || t->P.model == PT_TRANSE || t->P.model == PT_ROTATE || t->P.model == PT_DISTMULT ||
+                 t->P.model == PT_COMPLEX,
+             PT_ENOTSUP,
              "SigmoidLoss, adversarial weights and a model margin train TransE only (TransH is not implemented)");
     t->loss = L;
     return PT_OK;
@@ -607,8 +623,13 @@ extern "C" int pt_trainer_set_regul(pt_trainer *t, const pt_regul_desc *r) {
              PT_EINVAL, "pt_trainer_set_regul: regul_rate and l3_regul_rate must be finite and >= 0");
     PT_CHECK(r->batch_mode >= 0 && r->batch_mode <= 2, PT_EINVAL,
              "pt_trainer_set_regul: batch_mode must be 0 (normal), 1 (head_batch) or 2 (tail_batch)");
-    PT_CHECK(t->P.model == PT_DISTMULT || (r->regul_rate == 0.f && r->l3_regul_rate == 0.f), PT_ENOTSUP,
-             "regul_rate and l3_regul_rate train PT_DISTMULT only");
+    PT_CHECK(t->P.model != PT_COMPLEX || r->batch_mode == 0, PT_ENOTSUP,
+             "PT_COMPLEX takes batch_mode 0 (normal) only: ComplEx.forward ignores the batch mode");
+    PT_CHECK(t->P.model != PT_COMPLEX || r->l3_regul_rate == 0.f, PT_ENOTSUP,
+             "PT_COMPLEX has no l3 regulariser (ComplEx defines none): l3_regul_rate must be 0");
+    PT_CHECK(t->P.model == PT_DISTMULT || t->P.model == PT_COMPLEX ||
+                 (r->regul_rate == 0.f && r->l3_regul_rate == 0.f),
+             PT_ENOTSUP, "regul_rate trains PT_DISTMULT and PT_COMPLEX only, l3_regul_rate PT_DISTMULT only");
     t->regul.regul = r->regul_rate;
     t->regul.l3 = r->l3_regul_rate;
     t->regul.mode = r->batch_mode;
@@ -618,14 +639,15 @@ extern "C" int pt_trainer_set_regul(pt_trainer *t, const pt_regul_desc *r) {
 extern "C" int pt_trainer_set_adam(pt_trainer *t, const pt_adam_state *a) {
     PT_CHECK(t && a, PT_EINVAL, "pt_trainer_set_adam: null argument");
     PT_CHECK(a->ent_m && a->ent_v && a->rel_m && a->rel_v && (t->P.model != PT_TRANSH || (a->norm_m && a->norm_v)) &&
-                 (t->P.model != PT_TRANSD ||
+                 ((t->P.model != PT_TRANSD && t->P.model != PT_COMPLEX) ||
                   (a->ent_transfer_m && a->ent_transfer_v && a->rel_transfer_m && a->rel_transfer_v)),
              PT_EINVAL, "Adam needs exp_avg and exp_avg_sq buffers for every table");
     PT_CHECK(a->beta1 >= 0. && a->beta1 < 1. && a->beta2 >= 0. && a->beta2 < 1. && a->eps >= 0. && a->step >= 0,
              PT_EINVAL, "Adam: betas must be in [0, 1), eps and step non-negative");
     t->adam.m[0] = a->ent_m; t->adam.m[1] = a->rel_m; t->adam.m[2] = a->norm_m;
     t->adam.v[0] = a->ent_v; t->adam.v[1] = a->rel_v; t->adam.v[2] = a->norm_v;
-    const bool td = t->P.model == PT_TRANSD;   // (the appended fields are read for TransD only)
+    // (the appended fields are read for TransD and, as the im tables' moments, for ComplEx only)
+    const bool td = t->P.model == PT_TRANSD || t->P.model == PT_COMPLEX;
     t->adam.m[3] = td ? a->ent_transfer_m : nullptr; t->adam.m[4] = td ? a->rel_transfer_m : nullptr;
     t->adam.v[3] = td ? a->ent_transfer_v : nullptr; t->adam.v[4] = td ? a->rel_transfer_v : nullptr;
     t->adam.beta1 = a->beta1; t->adam.beta2 = a->beta2; t->adam.eps = a->eps;

@@ -379,6 +379,7 @@ extern "C" int pt_universe_set_create(const pt_universe_job *jobs, int64_t n, in
     PT_CHECK(model != PT_ROTATE, PT_ENOTSUP, "PT_ROTATE trains and ranks one model only: universes are not implemented");
     PT_CHECK(model != PT_DISTMULT, PT_ENOTSUP,
              "PT_DISTMULT trains and ranks one model only: universes are not implemented");
+    PT_CHECK(model != PT_COMPLEX, PT_ENOTSUP, "PT_COMPLEX trains and ranks one model only: universes are not implemented");
     PT_CHECK(model == 0 || model == 1, PT_EINVAL, "model must be 0 (TransE) or 1 (TransH)");
     PT_CHECK(p_norm == 1 || p_norm == 2, PT_EINVAL, "p_norm must be 1 or 2");
     PT_CHECK(opt == PT_SGD || opt == PT_ADAGRAD, PT_EINVAL, "opt must be PT_SGD or PT_ADAGRAD");

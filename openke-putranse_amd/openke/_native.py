@@ -20,7 +20,7 @@ c_u64p = ctypes.POINTER(ctypes.c_uint64)
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_f32p = ctypes.POINTER(ctypes.c_float)
 
-PT_TRANSE, PT_TRANSH, PT_TRANSD, PT_ROTATE, PT_DISTMULT = 0, 1, 2, 3, 4
+PT_TRANSE, PT_TRANSH, PT_TRANSD, PT_ROTATE, PT_DISTMULT, PT_COMPLEX = 0, 1, 2, 3, 4, 5
 PT_SGD, PT_ADAGRAD, PT_ADAM = 0, 1, 2
 PT_LOSS_MARGIN, PT_LOSS_SIGMOID = 0, 1
 PT_DETERMINISTIC = 1   # pt_universes_train_ex flag: reference-order (deterministic) mode
@@ -38,14 +38,15 @@ class ModelDesc(ctypes.Structure):
     _fields_ = [("model", c_i32), ("p_norm", c_i32), ("norm_flag", c_i32), ("opt", c_i32), ("lr", c_f32),
                 ("margin", c_f32), ("ent_total", c_i64), ("rel_total", c_i64), ("dim", c_i64), ("ent", c_vp),
                 ("rel", c_vp), ("normv", c_vp), ("ent_acc", c_vp), ("rel_acc", c_vp), ("norm_acc", c_vp),
-                # PT_TRANSD only (NULL otherwise)
+                # PT_TRANSD and PT_COMPLEX (its im tables) only (NULL otherwise)
                 ("ent_transfer", c_vp), ("rel_transfer", c_vp), ("ent_transfer_acc", c_vp), ("rel_transfer_acc", c_vp),
                 # PT_ROTATE only: the phase divisor rel_embedding_range / pi
                 ("phase_div", c_f32)]
 
 
 class RegulDesc(ctypes.Structure):
-    """pt_regul_desc: DistMult's regularisers and how the batch was handed over (pt_trainer_set_regul)."""
+    """pt_regul_desc: DistMult's regularisers (ComplEx: regul_rate only) and how the batch was handed over
+    (pt_trainer_set_regul)."""
     _fields_ = [("regul_rate", c_f32), ("l3_regul_rate", c_f32), ("batch_mode", c_i32)]
 
 
@@ -60,7 +61,7 @@ class AdamState(ctypes.Structure):
     _fields_ = [("ent_m", c_vp), ("rel_m", c_vp), ("norm_m", c_vp), ("ent_v", c_vp), ("rel_v", c_vp),
                 ("norm_v", c_vp), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
                 ("step", c_i64),
-                # PT_TRANSD only (NULL otherwise)
+                # PT_TRANSD and PT_COMPLEX (its im tables) only (NULL otherwise)
                 ("ent_transfer_m", c_vp), ("rel_transfer_m", c_vp), ("ent_transfer_v", c_vp), ("rel_transfer_v", c_vp)]
 
 

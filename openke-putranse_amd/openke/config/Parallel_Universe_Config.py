@@ -475,6 +475,9 @@ class Parallel_Universe_Config(Tester):
         if self.embedding_model.native_model == _native.PT_DISTMULT:
             raise NotImplementedError("DistMult trains and ranks one model (Trainer, Tester): its universes are not "
                                       "implemented")
+        if self.embedding_model.native_model == _native.PT_COMPLEX:
+            raise NotImplementedError("ComplEx trains and ranks one model (Trainer, Tester): its universes are not "
+                                      "implemented")
         _native.require_gpu()
 
     def _universe_draws(self, uid):

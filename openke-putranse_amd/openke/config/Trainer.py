@@ -13,7 +13,8 @@ and Adam (k_apply_adam, dense) for either model, and every TransD step (k_step_t
 Adagrad or Adam), and every RotatE step (k_step_rotate: SigmoidLoss or MarginLoss, with or without the adversarial
 weights, always on the model's margin; SGD, Adagrad or Adam), and every DistMult step (k_step_distmult: SigmoidLoss or
 SoftplusLoss - the same function - with or without the adversarial weights; regul_rate inside the step kernel with any
-optimizer, l3_regul_rate inside the Adam pass)."""
+optimizer, l3_regul_rate inside the Adam pass), and every ComplEx step (k_step_complex: the same losses and regul_rate
+on normal sampling; the optimizer pass runs over the re and over the im tables)."""
 import ctypes
 import os
 
@@ -79,7 +80,10 @@ class Trainer(object):
         kge, loss = ns.model, ns.loss
         if not isinstance(kge, Model) or kge.native_model is None:
             raise NotImplementedError("model %s is outside the accelerated path" % type(kge).__name__)
-        distmult = kge.native_model == _native.PT_DISTMULT
+        complex_ = kge.native_model == _native.PT_COMPLEX
+        distmult = kge.native_model == _native.PT_DISTMULT or complex_   # (the product-score family)
+        if complex_:
+            self._complex_refusals(ns, loss)
         if not isinstance(loss, (MarginLoss, SigmoidLoss)) and not (distmult and isinstance(loss, SoftplusLoss)):
             raise NotImplementedError("loss %s is outside the accelerated path (MarginLoss and SigmoidLoss are)"
                                       % type(loss).__name__)
@@ -87,7 +91,7 @@ class Trainer(object):
             raise NotImplementedError("MarginLoss on DistMult is outside the accelerated path (it would minimise the "
                                       "positive score): train DistMult under SigmoidLoss or SoftplusLoss")
         if self._weighted(kge, loss) and kge.native_model not in (_native.PT_TRANSE, _native.PT_ROTATE,
-                                                                  _native.PT_DISTMULT):
+                                                                  _native.PT_DISTMULT, _native.PT_COMPLEX):
             raise NotImplementedError("SigmoidLoss, adversarial temperature and a model margin are accelerated for "
                                       "TransE only")
         if (ns.regul_rate != 0 or ns.l3_regul_rate != 0) and not distmult:
@@ -97,6 +101,22 @@ class Trainer(object):
         if self.lr_decay != 0 or self.weight_decay != 0:
             raise NotImplementedError("lr_decay / weight_decay are 0 in the reference path")
         return ns, kge, loss
+
+    def _complex_refusals(self, ns, loss):
+        """What ComplEx does not train with, each by name (no device needed)."""
+        if isinstance(loss, MarginLoss):
+            raise NotImplementedError("MarginLoss on ComplEx is outside the accelerated path (it would minimise the "
+                                      "positive score): train ComplEx under SigmoidLoss or SoftplusLoss")
+        if ns.l3_regul_rate != 0:
+            raise NotImplementedError("l3_regul_rate on ComplEx: the model defines no l3_regularization (the reference "
+                                      "raises AttributeError)")
+        mode = getattr(self.data_loader, "sampling_mode", "normal")
+        if mode != "normal":
+            raise NotImplementedError("ComplEx trains on normal sampling only (sampling_mode %r): its forward ignores "
+                                      "the batch mode, so a cross-sampled batch does not broadcast in the reference "
+                                      "either" % (mode,))
+        if self.deterministic:
+            raise NotImplementedError("deterministic=True (reference-order mode) is not implemented for ComplEx")
 
     @staticmethod
     def _weighted(kge, loss):
@@ -170,9 +190,9 @@ class Trainer(object):
         return ns, kge, loss
 
     def _set_regul(self, ns, kge, mode):
-        """DistMult's regularisers and how the step's batch was handed over (0 normal, 1 head_batch, 2 tail_batch):
+        """DistMult's regularisers (ComplEx: regul_rate, normal mode only) and how the step's batch was handed over (0 normal, 1 head_batch, 2 tail_batch):
         pt_trainer_set_regul, called when either changes (cross sampling alternates the mode per step)."""
-        if kge.native_model != _native.PT_DISTMULT:
+        if kge.native_model not in (_native.PT_DISTMULT, _native.PT_COMPLEX):
             return
         key = (float(ns.regul_rate), float(ns.l3_regul_rate), int(mode))
         if key == self._regul_key:
@@ -185,7 +205,7 @@ class Trainer(object):
     def _external_only(self, kge, loss):
         """Whether every step goes through the external-batch step (k_step / k_step_adv + k_apply / k_apply_adam)."""
         return (self._weighted(kge, loss) or self.optimizer.method == _native.PT_ADAM
-                or kge.native_model in (_native.PT_TRANSD, _native.PT_ROTATE, _native.PT_DISTMULT))
+                or kge.native_model in (_native.PT_TRANSD, _native.PT_ROTATE, _native.PT_DISTMULT, _native.PT_COMPLEX))
 
     def _sync_step(self):
         if self.optimizer.method == _native.PT_ADAM:
@@ -217,6 +237,9 @@ class Trainer(object):
             # fp32 association only)
             if mode not in ('head_batch', 'tail_batch'):
                 raise ValueError("unknown batch mode %r" % (mode,))
+            if kge.native_model == _native.PT_COMPLEX:
+                raise NotImplementedError("ComplEx trains normal-mode batches only (mode %r): its forward ignores the "
+                                          "batch mode" % (mode,))
             full = h if mode == 'head_batch' else t
             rep = full.numel() // max(bs, 1)
             if mode == 'head_batch':

@@ -6,5 +6,6 @@ from .TransH import TransH
 from .TransD import TransD
 from .RotatE import RotatE
 from .DistMult import DistMult
+from .ComplEx import ComplEx
 
-__all__ = ['Model', 'TransE', 'TransH', 'TransD', 'RotatE', 'DistMult']
+__all__ = ['Model', 'TransE', 'TransH', 'TransD', 'RotatE', 'DistMult', 'ComplEx']
